@@ -14,9 +14,18 @@ output planes in HBM.  Inputs are synthetic (fuif_amd/synth.py, seeded) and are 
 host by the product's own FUIF writer (csrc/writer.cpp) before the timed region; K distinct
 images are replicated to the batch size and every replica is decoded independently.
 
-Output: ONE JSON line on rank 0 (see the task contract), with `roofline` for the dominant kernel
-and `cpu_baseline` = the reference decoder (oracle/_ref, kind "reference") or the oracle
-restatement (kind "port") timed single-threaded on this box's host cores on a bounded sample.
+Output: ONE JSON line on rank 0 (see the task contract).  A plain run sets up, warms up, times the
+`--steps` steps, writes the last step's outputs when `--dump-outputs DIR` is given and prints the
+headline line (metric, value, unit, ms_per_step, ...): it checks the decoder's status words and that
+replicas of one picture decoded alike, nothing that costs a run of its own.  `--full` adds
+everything else: parity against the source pixels, `roofline` for the dominant kernel (live PMC
+traffic), `cpu_baseline` = the reference decoder (oracle/_ref, kind "reference") or the oracle
+restatement (kind "port") timed single-threaded on this box's host cores on a bounded sample, the
+all-cores baseline, the no-index, reference-encoded, PCIe-inclusive and gather legs, and the
+other BASELINE configs (C3 / C4 / C5).
+
+Input streams are cached on disk (`--cache`, by default under the user's cache directory);
+`python bench.py --prepare-inputs` fills the cache for the default workload without a GPU.
 """
 import argparse
 import json
@@ -30,6 +39,27 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
+MAX_ENCODER_PROCS = 16   # the encoder pool never grows beyond this, whatever the host's core count
+
+
+def default_cache_dir():
+    """where encoded input streams are kept between runs: $FUIF_BENCH_CACHE, else the user's cache directory"""
+    if os.environ.get("FUIF_BENCH_CACHE"):
+        return os.environ["FUIF_BENCH_CACHE"]
+    base = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+    return os.path.join(base, "fuif_amd", "bench")
+
+
+def usable_cpus():
+    """CPUs this process may really use: the affinity mask and the container's CPU quota, not the machine's count"""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 1
+    quota = host_description().get("cgroup_cpu_quota")
+    if quota:
+        n = min(n, max(1, int(quota)))
+    return max(1, n)
 
 
 WORKLOADS = {
@@ -64,8 +94,9 @@ def _stream_path(cache_dir, kind, w, h, channels, bits, seed):
 
 
 def make_inputs_many(specs, cache_dir):
-    """specs: [(k, w, h, channels, bits, seed0, kind)] -> one list of (seed, stream bytes) per spec; everything that is not in the cache of this box
-    session is encoded by ONE pool of host processes (largest pictures first)."""
+    """specs: [(k, w, h, channels, bits, seed0, kind)] -> one list of (seed, stream bytes) per spec; everything that is not in the cache
+    is encoded by ONE pool of host processes (largest pictures first), at most one per usable CPU and MAX_ENCODER_PROCS in all, shared
+    out among the ranks of this node.  Call it before the process loads the HIP library: the pool forks."""
     os.makedirs(cache_dir, exist_ok=True)
     jobs, blobs = [], {}
     for k, w, h, channels, bits, seed0, kind in specs:
@@ -79,7 +110,8 @@ def make_inputs_many(specs, cache_dir):
     if jobs:
         import multiprocessing as mp
         jobs.sort(key=lambda j: -j[1] * j[2] * j[3])
-        nproc = max(1, min(len(jobs), (os.cpu_count() or 2)))
+        ranks_here = max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1")))
+        nproc = max(1, min(len(jobs), min(usable_cpus(), MAX_ENCODER_PROCS) // ranks_here))
         with mp.get_context("fork").Pool(nproc) as pool:
             for key, blob in pool.imap_unordered(_encode_keyed, jobs, chunksize=1):
                 blobs[key] = blob
@@ -447,7 +479,7 @@ def run_c5(args):
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     dist = fd.init(device=dev)
-    if dist is None and world == 1 and not args.no_rccl_selfcheck:
+    if dist is None and world == 1 and args.full and not args.no_rccl_selfcheck:
         try:   # one GPU: the gather below still goes through RCCL (a process group of one rank), see main()
             dist = fd.init(device=dev, world1=True)
         except Exception:   # noqa: BLE001
@@ -510,6 +542,9 @@ def run_c5(args):
         dec_ms.append(d); tr_ms.append(t)
     fence()
     elapsed = fd.max_over_ranks(time.perf_counter() - t0, dist, dev)
+    if args.dump_outputs and rank == 0:
+        # the last step's packed 8-bit pictures of this rank's shard (its first picture is global image lo)
+        write_outputs(args.dump_outputs, sample_outputs(packed.view(len(mine), pb), lo))
     # parity at size: the lossless half must be the generator's pixels; replicas of one source must be identical pictures
     pics = packed.view(len(mine), H, W, 3)
     for k in range(K):
@@ -554,7 +589,7 @@ def run_c5(args):
         res["roofline"] = {"bound": "hbm", "kernel": "k_maniac_decode", "achieved": round(alg / d_avg / 1e9, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                            "frac": round(alg / d_avg / 1e9 / HBM_PEAK_GBS, 6), "traffic": None, "kernel_ms": round(d_avg * 1e3, 3),
                            "algorithmic_bytes_per_launch": int(alg), "note": "kernel_ms / bytes = the sum over the step's launches (two kinds, chunks of %d) on rank 0" % chunk}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             mixed = [b for pair in zip([b for _, b in sq], [b for _, b in dc]) for b in pair]
             res["cpu_baseline"] = cpu_baseline(mixed, W, H)
             res["speedup_vs_cpu_1thread"] = round(value / res["cpu_baseline"]["value"], 2)
@@ -598,6 +633,7 @@ def run_streamed(args, wl, inputs, blobs, dev, dist, rank, world, W, H, C, BITS,
         torch.cuda.synchronize()
 
     def one_pass(check):
+        # (after a pass, `out` holds the last slice of its last chunk: pictures last[0] .. last[0] + last[1] - 1)
         ok, dec, tr, tiles = True, 0.0, 0.0, 0
         for c0 in range(0, args.batch, chunk):
             sub = blobs[c0:c0 + chunk]
@@ -608,6 +644,7 @@ def run_streamed(args, wl, inputs, blobs, dev, dist, rank, world, W, H, C, BITS,
                 cnt = min(n_slice, len(sub) - s0)
                 batch.undo_transforms_to(s0, cnt, out.data_ptr())
                 batch.sync()
+                last[:] = [c0 + s0, cnt]
                 d, t = batch.timing()
                 tr += t
                 if s0 == 0:
@@ -622,6 +659,7 @@ def run_streamed(args, wl, inputs, blobs, dev, dist, rank, world, W, H, C, BITS,
                 ok = ok and not st.any()
         return ok, dec, tr
 
+    last = [0, 0]
     ok = True
     checked = False
     for _ in range(args.warmup):
@@ -635,6 +673,8 @@ def run_streamed(args, wl, inputs, blobs, dev, dist, rank, world, W, H, C, BITS,
         dec_ms.append(d); tr_ms.append(t)
     fence()
     elapsed = fd.max_over_ranks(time.perf_counter() - t0, dist, dev)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, sample_outputs(out.view(n_slice, info.out_elems)[: last[1]], last[0]))
     if not checked:
         o, _, _ = one_pass(True)
         ok = ok and o
@@ -657,7 +697,7 @@ def run_streamed(args, wl, inputs, blobs, dev, dist, rank, world, W, H, C, BITS,
                             "frac": round(alg / d_avg / 1e9 / HBM_PEAK_GBS, 6), "traffic": None, "kernel_ms": round(d_avg * 1e3, 3),
                             "algorithmic_bytes_per_launch": int(alg), "note": "kernel_ms / bytes are per step = the sum over the step's chunk launches",
                             "transforms_ms": round(float(np.mean(tr_ms)), 3)}}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # (lossless workloads: the checker's own decode of stream 0 is compared with the generator's pixels as well -- at C4's real
             # size: real reference == source == every GPU-decoded picture)
             res["cpu_baseline"] = cpu_baseline([b for _, b in inputs], W, H, source=(inputs[0][0], C, BITS) if wl["lossless"] else None)
@@ -670,7 +710,7 @@ def run_streamed(args, wl, inputs, blobs, dev, dist, rank, world, W, H, C, BITS,
         raise SystemExit("PARITY FAILURE: decoded planes differ from the source pixels")
 
 
-def overlapped_steps(args, plan, blobs, dev, dist, W, H, index=True, warmup=None, steps=None):
+def overlapped_steps(args, plan, blobs, dev, dist, W, H, index=True, warmup=None, steps=None, keep_outputs=False):
     """The timed region of the default run: consecutive steps OVERLAP on the device (DESIGN.md 4.1 "overlapped launches").
 
     A launch is as long as the three long channel groups of a picture, and for its last 45 % they are all that runs: half of every
@@ -686,7 +726,8 @@ def overlapped_steps(args, plan, blobs, dev, dist, W, H, index=True, warmup=None
     EVERY step is verified: the caller compares every row of the table -- warm-up and timed steps alike -- with the checksums of the
     resident path's outputs, which it has compared with the generator's pixels (main()).
     Returns {elapsed (s, max over ranks, for args.steps steps between two fences), sums (device int64 [warmup + steps, n]),
-    launch_ms (own duration of the last launch of each batch object by its HIP events), status_ok, n_slice}."""
+    launch_ms (own duration of the last launch of each batch object by its HIP events), status_ok, n_slice, and with keep_outputs
+    `outputs`: sample_outputs() of the last timed step -- its last slice of pictures, still in its output tensor, and its checksum row}."""
     import torch
     import fuif_amd
     from fuif_amd import dist as fd
@@ -696,7 +737,7 @@ def overlapped_steps(args, plan, blobs, dev, dist, W, H, index=True, warmup=None
     streams = [torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)]
     # (zeros, not empty: planes are 256-byte aligned inside an image's slice and no kernel writes the gaps between them -- the per-image checksum covers
     # the whole slice, so the gaps must hold the same thing here and in the resident path's slab; a 3840x2160 plane happens to leave none)
-    warm = max(args.warmup, 1) if warmup is None else max(warmup, 0)
+    warm = max(args.warmup, 0) if warmup is None else max(warmup, 0)
     steps = args.steps if steps is None else steps
     cap = sum(len(b) for b in blobs) + 4096 * n
     batches, outs, sums = [], None, None
@@ -718,13 +759,13 @@ def overlapped_steps(args, plan, blobs, dev, dist, W, H, index=True, warmup=None
             raise
         if not fd.all_ok(True, dist, dev):
             raise RuntimeError("the overlapped region could not be set up on another rank")
-        return _overlapped_steps_on(args, plan, blobs, dev, dist, batches, streams, outs, sums, n, n_slice, warm, steps, index)
+        return _overlapped_steps_on(args, plan, blobs, dev, dist, batches, streams, outs, sums, n, n_slice, warm, steps, index, keep_outputs)
     finally:
         for b in batches:      # (also when an allocation or a launch failed: the caller falls back to the resident steps and needs the memory)
             b.close()
 
 
-def _overlapped_steps_on(args, plan, blobs, dev, dist, batches, streams, outs, sums, n, n_slice, warm, steps, index):
+def _overlapped_steps_on(args, plan, blobs, dev, dist, batches, streams, outs, sums, n, n_slice, warm, steps, index, keep_outputs=False):
     import torch
     import fuif_amd
     from fuif_amd import dist as fd
@@ -780,7 +821,13 @@ def _overlapped_steps_on(args, plan, blobs, dev, dist, batches, streams, outs, s
         st_words, _ = b.status()
         ok = ok and not st_words.any()
     launch_ms = [float(b.timing()[0]) for b in used]
-    return {"elapsed": elapsed, "sums": sums, "launch_ms": launch_ms, "status_ok": bool(ok), "n_slice": n_slice, "warm": warm, "steps": steps}
+    res = {"elapsed": elapsed, "sums": sums, "launch_ms": launch_ms, "status_ok": bool(ok), "n_slice": n_slice, "warm": warm, "steps": steps}
+    if keep_outputs and steps > 0:
+        # the last timed step ran on batch object (steps - 1) % 2; its output tensor still holds that step's last slice of pictures
+        s0 = (n - 1) // n_slice * n_slice
+        last = outs[(steps - 1) % 2].view(n_slice, info.out_elems)[: n - s0]
+        res["outputs"] = sample_outputs(last, s0, sums[warm + steps - 1])
+    return res
 
 
 def verify_overlapped(ov, out_ptr, out_elems, n, dev, stagger):
@@ -800,6 +847,95 @@ def verify_overlapped(ov, out_ptr, out_elems, n, dev, stagger):
             "stagger_s": stagger, "slice_images": ov["n_slice"], "launch_ms_overlapped": [round(x, 3) for x in ov["launch_ms"]]}
     del ov["sums"]
     return steps_ok, info
+
+
+DUMP_IMAGES = 4             # --dump-outputs: pictures sampled from what the last step left in memory
+DUMP_SAMPLES = 1 << 20      # output samples per sampled picture (4 x 4 MB of float32: the whole dump stays far below 64 MB)
+DUMP_SEED = 20261015
+
+
+def sample_outputs(planes, first, sums=None):
+    """--dump-outputs: a fixed, seeded sample of what a step computed -> {name: float array}.
+    planes: device tensor [m, elems] = the outputs of pictures first .. first + m - 1 of the step (int32 planes, or packed 8-bit samples);
+    sums: the step's per-picture 64-bit checksums (fuifgpu_plane_checksums), kept whole as two exact 32-bit halves.
+    The same arguments give the same pictures, positions and (for a correct build) values on every run."""
+    import torch
+    m, elems = int(planes.shape[0]), int(planes.shape[1])
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(m, size=min(m, DUMP_IMAGES), replace=False))
+    pos = np.sort(np.random.default_rng(DUMP_SEED + 1).choice(elems, size=min(elems, DUMP_SAMPLES), replace=False))   # (the same for every m)
+    rows = planes.index_select(0, torch.from_numpy(pick).to(planes.device))
+    vals = rows.index_select(1, torch.from_numpy(pos).to(planes.device)).to(torch.float32).cpu().numpy()   # (|values| < 2^24: exact)
+    out = {"planes_sample": vals, "planes_sample_pictures": (pick + first).astype(np.float64), "planes_sample_positions": pos.astype(np.float64)}
+    if sums is not None:
+        s = sums.cpu().numpy().astype(np.int64).view(np.uint64)
+        out["plane_checksums"] = np.stack([(s >> np.uint64(32)).astype(np.float64), (s & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=1)
+    return out
+
+
+def write_outputs(path, arrays):
+    """DIR/<name>.npy for every array of sample_outputs (float32 / float64 only)"""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def resident_checksums(out, info, n, dev):
+    """per-image checksums (fuifgpu_plane_checksums, as the overlapped steps record them) of the resident batch's outputs -> device int64 [n]"""
+    import torch
+    import fuif_amd
+    sums = torch.zeros(n, dtype=torch.int64, device=dev)
+    fuif_amd.plane_checksums(out.data_ptr(), info.out_elems, n, sums.data_ptr())
+    if dev.type == "cuda":
+        torch.cuda.synchronize()
+    return sums
+
+
+def finish_plain(args, wl, dist, dev, rank, world, K, S, elapsed, warm, value_mode, last_sums, status_ok, outputs, config, overlap_error=None):
+    """the end of a plain run (no --full): what costs nothing beyond the timed steps is checked -- the status words of the launches and that the
+    replicas of one picture (images k, k + K, ...) came out alike in the last step's checksums --, the outputs are written if asked, and the
+    headline line is printed.  Parity against the source pixels, the roofline and every other leg are --full's."""
+    from fuif_amd import dist as fd
+    W, H = args.width, args.height
+    ok = bool(status_ok) and bool((last_sums != 0).any().item())
+    for k in range(K):
+        ok = ok and bool((last_sums[k::K] == last_sums[k]).all().item())
+    ok = fd.all_ok(ok, dist, dev)
+    if rank == 0:
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
+        value = world * args.batch * W * H * args.steps / 1e6 / elapsed
+        res = {"metric": "Mpixels/s decode (4K Squeeze+YCoCg)" if args.workload == "c2" else "Mpixels/s decode (%s)" % args.workload, "value": round(value, 3),
+               "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": warm, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
+               "value_mode": value_mode, "scaling": "weak", "vs_baseline": None, "dtype": "int32", "data": "synthetic",
+               "config": dict({"workload": wl["desc"] % (args.batch, W, H), "images_per_gpu": args.batch, "distinct_images": K, "bytes_per_stream": int(S),
+                               "bits_per_pixel": round(8.0 * S / (W * H), 3),
+                               "group_index": "ignored (--no-index): one wavefront per image" if args.no_index else "FGIX trailer behind each stream: one wavefront per channel group",
+                               "status_ok_and_replicas_agree": ok,
+                               "checks": "status words of the launches; the last step's per-image checksums equal for every replica of a picture. Parity against "
+                                         "the source pixels, roofline, CPU baselines and the other legs: --full"}, **config)}
+        if overlap_error is not None:
+            res["config"]["overlapped_steps"] = "FAILED (%s): the timed steps are the resident batch's, one after the other, as with --no-overlap" % overlap_error
+        print(json.dumps(res))
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+    if not ok:
+        raise SystemExit("FAILURE: a launch reported an error or replicas of one picture decoded differently")
+
+
+def prepare_inputs(args):
+    """--prepare-inputs: the input streams a run with the same arguments on rank 0 decodes, encoded into --cache (host only)"""
+    if args.workload == "c5":
+        K = max(1, args.distinct // 2)
+        W, H = (args.width, args.height) if (args.width, args.height) != (3840, 2160) else (1920, 1080)
+        specs = [(K, W, H, 3, 8, 3000, "squeeze"), (K, W, H, 3, 8, 4000, "dct420")]
+    else:
+        wl = WORKLOADS[args.workload]
+        specs = [(max(1, min(args.distinct, args.batch)), args.width, args.height, wl["channels"], wl["bits"], 1000, wl["kind"])]
+    t0 = time.time()
+    made = make_inputs_many(specs, args.cache)
+    print(json.dumps({"prepared_streams": sum(len(m) for m in made), "cache": args.cache, "seconds": round(time.time() - t0, 1)}))
 
 
 def pmc_child(args):
@@ -953,7 +1089,13 @@ def main():
     ap.add_argument("--reference-encoded", type=int, default=4,
                     help="K pictures of the workload encoded by the REFERENCE encoder (oracle/_ref/fuif, default flags) on this box, given the group index "
                          "(fuif_amd.add_group_index), replicated to the batch and decoded on the resident batch: the `reference_encoded_streams` leg (0 = skip)")
-    ap.add_argument("--cache", default=os.environ.get("FUIF_BENCH_CACHE", "/tmp/fuif_bench_cache"))
+    ap.add_argument("--cache", default=default_cache_dir(), help="directory of the encoded input streams (default: $FUIF_BENCH_CACHE or the user's cache directory)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: parity against the source pixels, roofline with live PMC traffic, CPU baselines, the "
+                         "one-wavefront-per-picture, reference-encoded, PCIe-inclusive and gather legs, the RCCL self-check and the other BASELINE configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed, seeded sample of what the last timed step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--prepare-inputs", action="store_true", help="encode this workload's input streams into --cache and exit (host only, no GPU)")
     ap.add_argument("--no-rccl-selfcheck", action="store_true",
                     help="one GPU: do not start the one-rank RCCL process group that runs the N>1 collectives on cuda:0 (outside the timed region except for the fence's barrier)")
     ap.add_argument("--pmc-child", action="store_true", help="(internal) run the headline launch once and exit: what the live traffic measurement profiles")
@@ -966,12 +1108,13 @@ def main():
     if args.launcher_selftest:
         return launcher_selftest(args)
 
+    if args.prepare_inputs:
+        return prepare_inputs(args)
     import fuif_amd
     if args.pmc_child:
         return pmc_child(args)
     rank = int(os.environ.get("RANK", "0"))
     if args.workload == "c5":
-        fuif_amd.lib()
         return run_c5(args)
     # the HIP library is built by __graft_entry__.build() and travels in-tree; only a missing library is
     # built here, by local rank 0 alone (N ranks must not run hipcc on the same output file)
@@ -984,21 +1127,20 @@ def main():
                 if os.path.exists(lib_path):
                     break
                 time.sleep(1.0)
-    fuif_amd.lib()
     wl = WORKLOADS[args.workload]
     W, H, C, BITS = args.width, args.height, wl["channels"], wl["bits"]
     K = max(1, min(args.distinct, args.batch))
     # Inputs first: the encoder pool forks, so it runs before HIP, torch.distributed or any helper thread
     # exists in this process.  Rank r decodes its own images: distinct seeds per rank.
     ref_jobs = None
-    if args.reference_encoded > 0 and args.workload == "c2" and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_index and not args.chunk:
+    if args.full and args.reference_encoded > 0 and args.workload == "c2" and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_index and not args.chunk:
         try:
             ref_jobs = reference_encodes_start(min(args.reference_encoded, K), W, H, C, BITS, 1000, args.cache)
         except Exception:   # noqa: BLE001 -- an extra leg must not cost the bench line
             ref_jobs = None
     # the other BASELINE configs at small sizes (extra keys of the line): their streams come out of the same pool of encoder processes
     legs = {}
-    if args.workload == "c2" and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_extra_legs and not args.chunk and not args.no_index:
+    if args.full and args.workload == "c2" and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_extra_legs and not args.chunk and not args.no_index:
         legs = {name: spec for name, spec in EXTRA_LEGS.items() if name in args.extra_legs.split(",")}
     specs = [(K, W, H, C, BITS, 1000 + 100 * rank, wl["kind"])]
     for name, spec in legs.items():
@@ -1013,6 +1155,7 @@ def main():
     del made
     t_gen = time.time() - t0
     blobs = [inputs[i % K][1] for i in range(args.batch)]
+    fuif_amd.lib()     # (after the encoder pool: its processes must not inherit the HIP runtime)
 
     import torch
     from fuif_amd import dist as fd
@@ -1025,9 +1168,9 @@ def main():
     # One GPU: the collectives of the N>1 path still run, through a process group of ONE rank on RCCL (barrier, max-over-ranks
     # all_reduce, checksum all_gather, the chunked gather of the packed pictures), so that an RCCL / HIP-runtime clash in this
     # process shows on the one GPU the driver always has, not first on an 8-GPU node.  A failure to start RCCL is reported
-    # in the line (rccl_selfcheck), it does not stop the measurement; --no-rccl-selfcheck skips it.
+    # in the line (rccl_selfcheck), it does not stop the measurement; --no-rccl-selfcheck skips it.  A check: --full only.
     rccl_note = None
-    if dist is None and world == 1 and not args.no_rccl_selfcheck:
+    if dist is None and world == 1 and args.full and not args.no_rccl_selfcheck:
         try:
             dist = fd.init(device=dev, world1=True)
             probe = torch.ones(1, dtype=torch.int64, device=dev)
@@ -1059,7 +1202,7 @@ def main():
         # the timed ones, as with --no-overlap, and the line says why.  The ranks agree on the outcome inside overlapped_steps, before its first barrier.)
         overlap_error = None
         try:
-            ov = overlapped_steps(args, plan, blobs, dev, dist, W, H)
+            ov = overlapped_steps(args, plan, blobs, dev, dist, W, H, keep_outputs=bool(args.dump_outputs) and rank == 0)
         except (fuif_amd.FuifGpuError, RuntimeError, MemoryError) as e:
             ov, overlap_error = None, "%s: %s" % (type(e).__name__, str(e)[:300])
         import gc
@@ -1067,7 +1210,7 @@ def main():
         torch.cuda.empty_cache()
         # the same steps with the group index IGNORED (files as the reference CLI writes them: one wavefront per picture), overlapped the same way:
         # two launches in flight = two wavefronts per SIMD, which is what the wide kernel configuration is built for since round 5
-        if ov is not None and world == 1 and not args.no_seq_compare:
+        if ov is not None and world == 1 and args.full and not args.no_seq_compare:
             # (no warm-up step: the kernels have just run; an EVEN number of steps, so that every step has a partner beside it -- a step alone is 22 s)
             try:
                 ov_seq = overlapped_steps(args, plan, blobs, dev, dist, W, H, index=False, warmup=0, steps=max(2, args.seq_steps + (args.seq_steps & 1)))
@@ -1075,6 +1218,10 @@ def main():
                 ov_seq = None      # (the leg then shows the step alone only)
             gc.collect()
             torch.cuda.empty_cache()
+    S = sum(len(b) for b in blobs) / args.batch
+    if ov is not None and not args.full:
+        return finish_plain(args, wl, dist, dev, rank, world, K, S, ov["elapsed"], ov["warm"], "overlapped", ov["sums"][ov["warm"] + args.steps - 1],
+                            ov["status_ok"], ov.get("outputs"), {"input_gen_s": round(t_gen, 1)})
     out = torch.zeros(args.batch * info.out_elems, dtype=torch.int32, device=dev)     # (zeros: see overlapped_steps -- the checksums cover the alignment gaps between planes)
     batch = fuif_amd.Batch(plan, args.batch, int(sum(len(b) for b in blobs) * 1.03) + (1 << 20), out_ptr=out.data_ptr())   # (slack: the reference-encoded leg loads other streams)
     t0 = time.time()
@@ -1094,7 +1241,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    n_warm, n_timed = (1, max(1, args.alone_steps)) if ov is not None else (args.warmup, args.steps)
+    n_warm, n_timed = (1, max(1, args.alone_steps)) if ov is not None else (max(args.warmup, 0), args.steps)
     for _ in range(n_warm):
         step()
     fence()
@@ -1110,7 +1257,21 @@ def main():
     fence()
     elapsed_alone = fd.max_over_ranks(time.perf_counter() - t0, dist, dev)
     elapsed = ov["elapsed"] if ov is not None else elapsed_alone
-    warmup_done = ov["warm"] if ov is not None else n_warm   # (the overlapped region runs at least one warm-up step: the count that really ran goes into the line)
+    warmup_done = ov["warm"] if ov is not None else n_warm
+    dumped = None
+    if ov is None:
+        # the resident batch's steps were the timed ones: their outputs are all in `out` (the legs below reuse the batch)
+        last_sums = resident_checksums(out, info, args.batch, dev)
+        if not args.full:
+            st, _ = batch.status()
+            outputs = sample_outputs(out.view(args.batch, info.out_elems), 0, last_sums) if args.dump_outputs and rank == 0 else None
+            batch.close()
+            return finish_plain(args, wl, dist, dev, rank, world, K, S, elapsed, warmup_done, "sequential", last_sums, not st.any(), outputs,
+                                {"input_gen_s": round(t_gen, 1), "upload_s": round(t_upload, 3)}, overlap_error)
+        if args.dump_outputs and rank == 0:
+            dumped = sample_outputs(out.view(args.batch, info.out_elems), 0, last_sums)
+    elif args.dump_outputs and rank == 0:
+        dumped = ov.pop("outputs")
 
     # ---- correctness at full size: lossless round trip against the generator's pixels ----------
     from fuif_amd.synth import photographic
@@ -1384,7 +1545,6 @@ def main():
             live_traffic, live_src = None, "%s: %s" % (type(e).__name__, str(e)[:200])
 
     if rank == 0:
-        S = sum(len(b) for b in blobs) / args.batch
         N = info.coef_elems
         P = info.out_elems
         # dominant kernel: k_maniac_decode reads the stream once and writes every coefficient once -- as an int16 sample since round 4
@@ -1479,6 +1639,8 @@ def main():
                     allc = cpu_baseline_all_cores(paths, W, H)
                     if allc:
                         res["cpu_baseline_all_cores"] = allc
+        if dumped is not None:
+            write_outputs(args.dump_outputs, dumped)
         print(json.dumps(res))
     if dist is not None:
         dist.barrier()

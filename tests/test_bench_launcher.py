@@ -55,7 +55,7 @@ def test_bench_main_runs_end_to_end_on_two_gloo_ranks_over_the_emulated_library(
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "tests", "_bench_on_emulator.py"), "--gpus", "2", "--batch", "4", "--width", "97", "--height", "61", "--distinct", "2", "--steps", "2", "--warmup", "1",
-           "--slice", "3", "--no-live-traffic", "--no-cpu-all-cores"]
+           "--slice", "3", "--no-live-traffic", "--no-cpu-all-cores", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-2500:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -82,7 +82,7 @@ def test_bench_main_default_path_on_one_emulated_rank(tmp_path):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "tests", "_bench_on_emulator.py"), "--gpus", "1", "--batch", "4", "--width", "97", "--height", "61", "--distinct", "2",
            "--steps", "1", "--warmup", "1", "--seq-steps", "2", "--alone-steps", "1", "--slice", "3", "--no-live-traffic", "--no-cpu-all-cores", "--no-extra-legs",
-           "--no-rccl-selfcheck", "--reference-encoded", "2"]
+           "--no-rccl-selfcheck", "--reference-encoded", "2", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-2500:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -114,10 +114,57 @@ def test_bench_line_survives_an_overlapped_region_that_cannot_be_set_up(tmp_path
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "tests", "_bench_on_emulator.py"), "--gpus", "2", "--batch", "3", "--width", "97", "--height", "61", "--distinct", "2", "--steps", "2", "--warmup", "1",
-           "--no-live-traffic", "--no-cpu-all-cores"]
+           "--no-live-traffic", "--no-cpu-all-cores", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-2500:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["config"]["parity_roundtrip_ok"] is True and d["value"] > 0
     assert d["config"]["overlapped_steps"].startswith("FAILED") and "no memory for a streaming batch" in d["config"]["overlapped_steps"]
     assert "overlap" not in d and "kernel_ms" in d["roofline"] and d["cpu_baseline"]["value"] > 0
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_the_last_step(tmp_path):
+    """without --full the line is the headline figure alone (no CPU baseline, no extra legs, no parity pass of its own), --steps sets the timed
+    steps, and --dump-outputs writes the last timed step's outputs: the same float arrays on a second run with the same arguments, and the
+    sampled samples equal to what the resident path (--no-overlap) decodes for the same pictures"""
+    import numpy as np
+    if sys.platform != "linux" or os.uname().machine != "x86_64":
+        import pytest
+        pytest.skip("the emulator's context switch is x86-64 SysV assembly")
+    from test_emulated_kernels import build_emulated_library
+    env = dict(os.environ, FUIF_AMD_LIB=build_emulated_library(), EMU_ALARM="900", FUIF_BENCH_CACHE=str(tmp_path / "cache"))
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    base = [sys.executable, os.path.join(ROOT, "tests", "_bench_on_emulator.py"), "--gpus", "1", "--batch", "5", "--width", "97", "--height", "61", "--distinct", "2",
+            "--steps", "3", "--warmup", "0", "--slice", "2"]
+    dumps = []
+    for i, extra in enumerate(([], [], ["--no-overlap"])):
+        out = tmp_path / ("out%d" % i)
+        r = subprocess.run(base + extra + ["--dump-outputs", str(out)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-2500:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-1500:]
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["steps"] == 3 and d["warmup"] == 0 and d["value"] > 0 and d["ms_per_step"] > 0 and d["config"]["status_ok_and_replicas_agree"] is True
+        assert d["value_mode"] == ("sequential" if extra else "overlapped")
+        for key in ("cpu_baseline", "roofline", "other_configs", "one_wavefront_per_image", "h2d", "final_gather", "single_launch"):
+            assert key not in d, key
+        arrays = {f[:-4]: np.load(str(out / f)) for f in os.listdir(str(out))}
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        dumps.append(arrays)
+    a, b, c = dumps
+    assert sorted(a) == sorted(b) == sorted(c) == ["plane_checksums", "planes_sample", "planes_sample_pictures", "planes_sample_positions"]
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+    # overlapped (last slice of the last step: pictures 4) and resident (all 5 pictures) runs: the same checksums, the same samples per picture
+    assert np.array_equal(a["plane_checksums"], c["plane_checksums"]) and a["plane_checksums"].shape == (5, 2)
+    assert np.array_equal(a["planes_sample_positions"], c["planes_sample_positions"])
+    by_source = {}     # (picture p decodes stream p % 2: --distinct 2)
+    for p, row in zip(c["planes_sample_pictures"], c["planes_sample"]):
+        by_source.setdefault(int(p) % 2, row)
+        assert np.array_equal(row, by_source[int(p) % 2])
+    assert list(a["planes_sample_pictures"]) == [4.0] and np.array_equal(a["planes_sample"][0], by_source[0])
+    assert a["planes_sample"].max() > 0

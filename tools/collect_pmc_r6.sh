@@ -15,7 +15,7 @@ done
 for pat in write write32; do
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/cal_${pat} -- $G $pat 20000 > $OUT/cal_${pat}.json 2> $OUT/cal_${pat}.err
 done
-BENCH="python $ROOT/bench.py --no-cpu-baseline --no-seq-compare --no-h2d --no-live-traffic --no-extra-legs --reference-encoded 0 --no-rccl-selfcheck --no-overlap"
+BENCH="python $ROOT/bench.py --full --no-cpu-baseline --no-seq-compare --no-h2d --no-live-traffic --no-extra-legs --reference-encoded 0 --no-rccl-selfcheck --no-overlap"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- $BENCH --steps 1 --warmup 0 > $OUT/bench_fetch.json 2> $OUT/bench_fetch.err
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- $BENCH --steps 1 --warmup 0 > $OUT/bench_write.json 2> $OUT/bench_write.err
 python $ROOT/tools/summarize_pmc_r6.py $OUT > $OUT/summary.txt 2>&1

@@ -12,12 +12,12 @@ OUT=$ROOT/gpurun_out/prof_r5
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 COMMON="--no-cpu-baseline --no-seq-compare --no-h2d --no-live-traffic --no-extra-legs --reference-encoded 0 --no-rccl-selfcheck"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/alone -- python $ROOT/bench.py $COMMON --no-overlap --steps 2 --warmup 1 > $OUT/bench_alone.json 2> $OUT/bench_alone.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/overlapped -- python $ROOT/bench.py $COMMON --steps 4 --warmup 1 --alone-steps 1 > $OUT/bench_overlapped.json 2> $OUT/bench_overlapped.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c3 -- python $ROOT/bench.py --workload c3 --no-overlap --steps 3 --warmup 1 $COMMON > $OUT/bench_c3.json 2> $OUT/bench_c3.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/alone -- python $ROOT/bench.py --full $COMMON --no-overlap --steps 2 --warmup 1 > $OUT/bench_alone.json 2> $OUT/bench_alone.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/overlapped -- python $ROOT/bench.py --full $COMMON --steps 4 --warmup 1 --alone-steps 1 > $OUT/bench_overlapped.json 2> $OUT/bench_overlapped.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c3 -- python $ROOT/bench.py --full --workload c3 --no-overlap --steps 3 --warmup 1 $COMMON > $OUT/bench_c3.json 2> $OUT/bench_c3.err
 cd $ROOT
 for d in alone overlapped c3; do find $OUT/$d -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/${d}_kernel_stats.csv; rm -rf $OUT/$d; done
-timeout 300 python bench.py --workload c5 --batch 2048 --steps 2 --warmup 1 --no-rccl-selfcheck > $OUT/bench_c5_2048.json 2> $OUT/bench_c5_2048.err
+timeout 300 python bench.py --full --workload c5 --batch 2048 --steps 2 --warmup 1 --no-rccl-selfcheck > $OUT/bench_c5_2048.json 2> $OUT/bench_c5_2048.err
 python - <<'P' | tee $OUT/summary.txt
 import csv, json, os
 out = os.path.join(os.environ.get("GRAFT_REPO_ROOT", os.getcwd()), "gpurun_out", "prof_r5")
@@ -44,5 +44,5 @@ try:
 except Exception as e:
     print("== C5: failed", e)
 P
-(time timeout 900 python bench.py --steps 10 --warmup 2) > $OUT/bench_default.json 2> $OUT/bench_default.err
+(time timeout 900 python bench.py --full --steps 10 --warmup 2) > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -c 1500 $OUT/bench_default.json

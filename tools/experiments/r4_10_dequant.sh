@@ -13,4 +13,4 @@ if ! grep -q " passed" $OUT/gpu_tests.txt || grep -q "failed\|error" $OUT/gpu_te
 timeout 200 python tools/time_decode.py 1024 3840 2160 --dct420 --reps 3
 FUIFGPU_INT16_RESIDUALS=0 timeout 200 python tools/time_decode.py 1024 3840 2160 --dct420 --reps 3
 } 2>&1 | grep -v amdgpu | tee $OUT/times.txt
-timeout 600 python bench.py --workload c3 --no-live-traffic > $OUT/bench_c3.json 2> $OUT/bench_c3.err; tail -c 1500 $OUT/bench_c3.json
+timeout 600 python bench.py --full --workload c3 --no-live-traffic > $OUT/bench_c3.json 2> $OUT/bench_c3.err; tail -c 1500 $OUT/bench_c3.json

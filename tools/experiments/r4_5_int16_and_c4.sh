@@ -16,4 +16,4 @@ for lib in build/libfuifgpu_trims2.so fuif_amd/libfuifgpu.so build/libfuifgpu_tr
   FUIF_AMD_LIB=$ROOT/$lib timeout 200 python tools/time_decode.py 1024 3840 2160 --reps 2 --check
 done
 } 2>&1 | grep -v amdgpu | tee $OUT/times.txt
-FUIFGPU_CTX_MB=32 timeout 900 python bench.py --workload c4 --width 8192 --height 8192 --batch 256 --chunk -1 --distinct 2 --steps 1 --warmup 0 > $OUT/bench_c4.json 2> $OUT/bench_c4.err; tail -c 2500 $OUT/bench_c4.json; tail -5 $OUT/bench_c4.err
+FUIFGPU_CTX_MB=32 timeout 900 python bench.py --full --workload c4 --width 8192 --height 8192 --batch 256 --chunk -1 --distinct 2 --steps 1 --warmup 0 > $OUT/bench_c4.json 2> $OUT/bench_c4.err; tail -c 2500 $OUT/bench_c4.json; tail -5 $OUT/bench_c4.err

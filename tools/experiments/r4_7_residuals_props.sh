@@ -16,4 +16,4 @@ FUIFGPU_INT16_RESIDUALS=0 timeout 200 python tools/time_decode.py 1024 3840 2160
 timeout 200 python tools/time_decode.py 1024 3840 2160 --no-index --reps 2 --check
 timeout 200 python tools/time_decode.py 1024 3840 2160 --dct420 --reps 2
 } 2>&1 | grep -v amdgpu | tee $OUT/times.txt
-timeout 600 python bench.py --workload c5 --batch 2048 --steps 1 --warmup 1 > $OUT/bench_c5.json 2> $OUT/bench_c5.err; tail -c 1800 $OUT/bench_c5.json; grep -v "File\|^    \|amdgpu.ids" $OUT/bench_c5.err | tail -3
+timeout 600 python bench.py --full --workload c5 --batch 2048 --steps 1 --warmup 1 > $OUT/bench_c5.json 2> $OUT/bench_c5.err; tail -c 1800 $OUT/bench_c5.json; grep -v "File\|^    \|amdgpu.ids" $OUT/bench_c5.err | tail -3

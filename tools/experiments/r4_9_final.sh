@@ -9,6 +9,6 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $ROOT
 OUT=gpurun_out/r4_final2
 mkdir -p $OUT
-(time timeout 900 python bench.py) > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 1200 $OUT/bench_default.json; grep -v "File\|^    \|amdgpu.ids" $OUT/bench_default.err | tail -4
+(time timeout 900 python bench.py --full) > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 1200 $OUT/bench_default.json; grep -v "File\|^    \|amdgpu.ids" $OUT/bench_default.err | tail -4
 timeout 900 bash tools/collect_profiles_r4.sh > $OUT/collect.txt 2>&1; tail -28 $OUT/collect.txt
 (time timeout 1200 python -m pytest tests -m gpu -x -q) > $OUT/gpu_tests.txt 2>&1; tail -5 $OUT/gpu_tests.txt

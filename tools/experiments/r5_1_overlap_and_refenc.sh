@@ -14,5 +14,5 @@ mkdir -p $OUT
 tail -n 6 $OUT/tests.txt
 timeout 400 python tools/pipeline_decode.py 1024 --launches 6 --stagger 3.6 --rounds 1 2>&1 | grep -v amdgpu | tee $OUT/entropy_stagger36.txt
 timeout 300 python tools/pipeline_decode.py 1024 --launches 6 --stagger 0 --rounds 1 --only-pipelined 2>&1 | grep -v amdgpu | tee $OUT/entropy_at_once.txt
-(time timeout 900 python bench.py --steps 8 --warmup 2 --no-cpu-all-cores) > $OUT/bench_default.json 2> $OUT/bench_default.err
+(time timeout 900 python bench.py --full --steps 8 --warmup 2 --no-cpu-all-cores) > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -c 6000 $OUT/bench_default.json; tail -n 8 $OUT/bench_default.err | grep -v amdgpu

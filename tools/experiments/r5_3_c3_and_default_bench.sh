@@ -14,12 +14,12 @@ mkdir -p $OUT
 tail -n 5 $OUT/tests.txt
 C3="--workload c3 --no-overlap --steps 3 --warmup 1 --no-seq-compare --no-h2d --no-cpu-all-cores --no-rccl-selfcheck"
 cd /tmp && export TMPDIR=/tmp
-timeout 400 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/c3_prof -o c3 -- python $ROOT/bench.py $C3 > $ROOT/$OUT/bench_c3_under_rocprof.json 2> $ROOT/$OUT/bench_c3_under_rocprof.err
+timeout 400 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/c3_prof -o c3 -- python $ROOT/bench.py --full $C3 > $ROOT/$OUT/bench_c3_under_rocprof.json 2> $ROOT/$OUT/bench_c3_under_rocprof.err
 cd $ROOT
 find $OUT/c3_prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/c3_kernel_stats.csv
 head -n 14 $OUT/c3_kernel_stats.csv
 rm -rf $OUT/c3_prof
-FUIFGPU_FUSE_DEQUANT=0 FUIFGPU_FUSE_YCBCR=0 timeout 300 python bench.py $C3 --no-cpu-baseline > $OUT/bench_c3_unfused.json 2> $OUT/bench_c3_unfused.err
+FUIFGPU_FUSE_DEQUANT=0 FUIFGPU_FUSE_YCBCR=0 timeout 300 python bench.py --full $C3 --no-cpu-baseline > $OUT/bench_c3_unfused.json 2> $OUT/bench_c3_unfused.err
 python - <<'P'
 import json
 for f in ("bench_c3_under_rocprof", "bench_c3_unfused"):
@@ -29,5 +29,5 @@ for f in ("bench_c3_under_rocprof", "bench_c3_unfused"):
     except Exception as e:
         print(f, "failed", e)
 P
-(time timeout 900 python bench.py --steps 6 --warmup 2 --no-cpu-all-cores) > $OUT/bench_default.json 2> $OUT/bench_default.err
+(time timeout 900 python bench.py --full --steps 6 --warmup 2 --no-cpu-all-cores) > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -c 3000 $OUT/bench_default.json; tail -n 6 $OUT/bench_default.err | grep -v amdgpu

@@ -11,14 +11,14 @@ mkdir -p $OUT
 tail -n 8 $OUT/gpu_tests.txt
 C3="--workload c3 --no-overlap --steps 3 --warmup 1 --no-seq-compare --no-h2d --no-cpu-all-cores --no-rccl-selfcheck"
 cd /tmp && export TMPDIR=/tmp
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/c3_prof -- python $ROOT/bench.py $C3 > $ROOT/$OUT/bench_c3_under_rocprof.json 2> $ROOT/$OUT/bench_c3_under_rocprof.err
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/c3_prof -- python $ROOT/bench.py --full $C3 > $ROOT/$OUT/bench_c3_under_rocprof.json 2> $ROOT/$OUT/bench_c3_under_rocprof.err
 cd $ROOT
 find $OUT/c3_prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/c3_kernel_stats.csv
 head -n 16 $OUT/c3_kernel_stats.csv
 rm -rf $OUT/c3_prof
-FUIFGPU_FUSE_DEQUANT=0 FUIFGPU_FUSE_YCBCR=0 timeout 300 python bench.py $C3 --no-cpu-baseline > $OUT/bench_c3_unfused.json 2> $OUT/bench_c3_unfused.err
-FUIFGPU_FUSE_DEQUANT=1 FUIFGPU_FUSE_YCBCR=0 timeout 300 python bench.py $C3 --no-cpu-baseline > $OUT/bench_c3_dequant_only.json 2> $OUT/bench_c3_dequant_only.err
-timeout 300 python bench.py --workload c3 --steps 6 --warmup 2 --no-seq-compare --no-h2d --no-cpu-all-cores --no-rccl-selfcheck --no-cpu-baseline > $OUT/bench_c3_overlapped.json 2> $OUT/bench_c3_overlapped.err
+FUIFGPU_FUSE_DEQUANT=0 FUIFGPU_FUSE_YCBCR=0 timeout 300 python bench.py --full $C3 --no-cpu-baseline > $OUT/bench_c3_unfused.json 2> $OUT/bench_c3_unfused.err
+FUIFGPU_FUSE_DEQUANT=1 FUIFGPU_FUSE_YCBCR=0 timeout 300 python bench.py --full $C3 --no-cpu-baseline > $OUT/bench_c3_dequant_only.json 2> $OUT/bench_c3_dequant_only.err
+timeout 300 python bench.py --full --workload c3 --steps 6 --warmup 2 --no-seq-compare --no-h2d --no-cpu-all-cores --no-rccl-selfcheck --no-cpu-baseline > $OUT/bench_c3_overlapped.json 2> $OUT/bench_c3_overlapped.err
 python - <<'P'
 import json
 for f in ("bench_c3_under_rocprof", "bench_c3_unfused", "bench_c3_dequant_only", "bench_c3_overlapped"):

@@ -11,12 +11,12 @@ mkdir -p $OUT
 tail -n 4 $OUT/tests.txt
 C3="--workload c3 --no-overlap --steps 3 --warmup 1 --no-seq-compare --no-h2d --no-cpu-all-cores --no-rccl-selfcheck --no-live-traffic --no-extra-legs --reference-encoded 0"
 cd /tmp && export TMPDIR=/tmp
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/c3_prof -- python $ROOT/bench.py $C3 > $ROOT/$OUT/bench_c3_under_rocprof.json 2> $ROOT/$OUT/bench_c3_under_rocprof.err
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/c3_prof -- python $ROOT/bench.py --full $C3 > $ROOT/$OUT/bench_c3_under_rocprof.json 2> $ROOT/$OUT/bench_c3_under_rocprof.err
 cd $ROOT
 find $OUT/c3_prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/c3_kernel_stats.csv
 rm -rf $OUT/c3_prof
 grep -i "idct\|ups2\|maniac\|dequant\|widen" $OUT/c3_kernel_stats.csv | cut -c1-200
-FUIFGPU_FUSE_DEQUANT=0 timeout 300 python bench.py $C3 --no-cpu-baseline > $OUT/bench_c3_no_dequant_fusion.json 2> $OUT/bench_c3_no_dequant_fusion.err
+FUIFGPU_FUSE_DEQUANT=0 timeout 300 python bench.py --full $C3 --no-cpu-baseline > $OUT/bench_c3_no_dequant_fusion.json 2> $OUT/bench_c3_no_dequant_fusion.err
 python - <<'P'
 import json
 for f in ("bench_c3_under_rocprof", "bench_c3_no_dequant_fusion"):
