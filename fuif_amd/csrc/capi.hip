@@ -452,7 +452,7 @@ int fuifgpu_batch_upload(fuifgpu_batch *b, const uint8_t *const *blobs, const si
     // image in stream order, images dealt to one queue per CU, a tile that would wait for another tile's rows is
     // suspended instead of holding its wavefront (measured on 1024 x 4K: a quarter of all wavefront time was spent in
     // such waits, profiles/r2_tile_timeline_baseline.txt).  Otherwise -- and with FUIFGPU_TILE_ORDER=group, a diagnostic
-    // -- one group-major list as in round 1: tile k of every image before tile k+1 of any.
+    // -- one group-major list: tile k of every image before tile k+1 of any.
     const char *ord = getenv("FUIFGPU_TILE_ORDER");
     b->sched = b->dense && (int64_t)total_tiles > b->n_waves && !(ord && !strcmp(ord, "group")) ? 1 : 0;
     b->tiles.clear();
@@ -497,7 +497,7 @@ int fuifgpu_batch_upload(fuifgpu_batch *b, const uint8_t *const *blobs, const si
     {
         // scheduler state, zeroed before every launch: q_head | done_total | statistics | started_total | heartbeat | cu claim table |
         // cu_alive | cu_live | cu_foreign | img_next | img_done | ctx_used | tile records
-        const size_t words = 24 + (2 * 4096 + 1) + 3 * 4096 + 4 * 4096 + 2 * (size_t)n_images + 2 * (size_t)b->n_queues + (b->sched ? (size_t)b->n_tiles * (sizeof(TileRec) / 4) : 0);
+        const size_t words = 24 + (2 * 4096 + 1) + 3 * 4096 + 4 * 4096 + 2 * (size_t)n_images + (size_t)b->n_queues + (b->sched ? (size_t)b->n_tiles * (sizeof(TileRec) / 4) : 0);
         if (words > b->sched_words) {
             hipFree(b->d_sched); b->d_sched = nullptr; b->sched_words = 0;
             HIPCHK(hipMalloc((void **)&b->d_sched, words * 4));
@@ -591,7 +591,7 @@ int fuifgpu_batch_decode(fuifgpu_batch *b, void *stream) {
         P.q_head = w; P.done_total = w + 1; P.sched_stats = reinterpret_cast<unsigned long long *>(w + 2); P.started_total = w + 18; P.heartbeat = w + 19;
         P.ctx_used = reinterpret_cast<unsigned long long *>(w + 20);   // (byte offset 80: 8-byte aligned)
         w += 24;
-        P.yield_slack = 4;   // (round 4, profiles/r4_scheduler_knobs.txt: 4 -> 7.30 s, 8 -> 7.37 s, 16 -> 7.60 s, 32 -> 7.83 s on the trimmed kernel)
+        P.yield_slack = 4;   // (profiles/r4_scheduler_knobs.txt: 4 -> 7.30 s, 8 -> 7.37 s, 16 -> 7.60 s, 32 -> 7.83 s on the trimmed kernel)
         if (const char *e = getenv("FUIFGPU_YIELD_SLACK")) P.yield_slack = (uint32_t)std::max(0, atoi(e));
         P.prio_base = kDefaultPrioBase;   // size classes <= base run at wavefront priority 3, base+1 at 2, base+2 at 1; negative: all 0
         if (const char *e = getenv("FUIFGPU_PRIO_BASE")) P.prio_base = atoi(e);
@@ -602,7 +602,6 @@ int fuifgpu_batch_decode(fuifgpu_batch *b, void *stream) {
         if (const char *e = getenv("FUIFGPU_LONG_PER_SIMD")) P.long_per_simd = std::max(0, atoi(e));
         P.img_next = w; w += b->n_loaded;
         P.img_done = w; w += b->n_loaded;
-        w += b->n_queues;   // (rounds 2-5: one bump counter per queue)
         P.q_turn = w; w += b->n_queues;
         P.tile_rec = reinterpret_cast<TileRec *>(w);
         P.q_img_begin = b->d_layout; P.q_images = b->d_layout + b->n_queues + 1; P.img_tile_begin = b->d_layout + b->n_queues + 1 + b->n_loaded;
@@ -668,7 +667,7 @@ int fuifgpu_batch_undo_transforms(fuifgpu_batch *b, void *stream) {
     if (!b || b->n_loaded < 1) return FUIFGPU_E_ARG;
     if (b->no_out) { g_last_error = "fuifgpu_batch_undo_transforms: a streaming batch has no output slab (fuifgpu_batch_undo_transforms_to)"; return FUIFGPU_E_ARG; }
     for (char u : b->undone) if (u) { g_last_error = "fuifgpu_batch_undo_transforms: part of this decode went through fuifgpu_batch_undo_transforms_to already"; return FUIFGPU_E_ARG; }
-    // The inverse kernels work on a widened COPY of the coefficients (round 4), so the slab itself stays as decoded; but
+    // The inverse kernels work on a widened COPY of the coefficients, so the slab itself stays as decoded; but
     // Approximate rewrites ChannelMeta::q, which a second pass over the same decode would apply twice
     if (b->coef_consumed) { g_last_error = "fuifgpu_batch_undo_transforms: already run on this decode (it rewrites the channel metadata); decode again first"; return FUIFGPU_E_ARG; }
     b->coef_consumed = true;

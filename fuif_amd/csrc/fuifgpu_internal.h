@@ -18,14 +18,14 @@ constexpr int kMaxBitDepth = 15;        // config.h:5 (MAX_BIT_DEPTH)
 constexpr int kNonRefProps = 13;        // encoding/context_predict.h:210
 constexpr int kMaxProps = 64;           // 2*6 reference properties + 13 local ones = 25 at default options; one property per lane of the wavefront
 constexpr int kMaxRefs = 25;            // 2*25 + 13 = 63 properties: what the 64 lanes hold (-E 50).  Up to 9 references (31 properties, -E 18) a chunk's
-                                        // property rows have 33 words and the chunk its full length; beyond, 65 words and half the pixels (round 4)
+                                        // property rows have 33 words and the chunk its full length; beyond, 65 words and half the pixels
 constexpr int kFastRefs = 9;            // references whose loads the vector phase issues together (unrolled); further ones go through a loop
 constexpr int kMaxNodes = 65535;        // childID is uint16_t (maniac/compound.h:46)
 constexpr int kLeafStride = 32;         // 31 chances (maniac/symbol.h:72-77) padded to 64 bytes
 constexpr int kTreeStackDepth = 2048;   // explicit stack replacing the recursion of compound.h:277-308
 constexpr int kPlaneAlign = 128;        // planes start on 256-byte boundaries inside a slab (coefficient slab: 128 int16 elements)
 // A coded sample is a pixel_type = int16_t in the reference (image/image.h:35; check_bit_depth caps compressed samples at 15 bits
-// of magnitude, encoding.cpp:61-72): the coefficient slab the entropy kernel writes holds int16 samples (round 4: half the slab,
+// of magnitude, encoding.cpp:61-72): the coefficient slab the entropy kernel writes holds int16 samples (half the slab of int32 ones,
 // twice the images per launch for C4).  The inverse transforms compute in int32: they run on a widened copy of a chunk of images.
 using coef_t = int16_t;
 
@@ -75,7 +75,7 @@ struct Tile {
     uint32_t flags;                       // bit 0: every tile of this image is one single-channel group, so every tile that can wait for
                                           // another tile's rows can be SUSPENDED (context scheduler).  Otherwise none of the image's
                                           // tiles is: a suspended tile needs a free wavefront to go on, and tiles that wait by
-                                          // spinning could hold all of them (round 1's invariant -- a taken tile runs -- per image)
+                                          // spinning could hold all of them (the invariant that a taken tile runs, kept per image)
 };
 constexpr uint32_t kTileSuspendable = 1u;
 constexpr uint32_t kTileSizeClassShift = 4;   // bits 4..7: floor(log2(image samples / tile samples)), 15 = empty tile

@@ -31,21 +31,19 @@
 // A single wave issues one instruction every ~4.6 cycles, a taken branch costs ~25 and a
 // VALU<->SALU hand-over ~14 (tools/ubench.hip), so the kernel is bound by the instruction count of
 // the per-symbol chain (and by two dependent HBM round trips per symbol: a supernode, the leaf); every
-// item above trades scalar instructions for vector ones.  Measured on the 1024 x 4K launch (round 4,
-// profiles/r4_instruction_probes.txt): one more scalar instruction per symbol costs 0.37 % of the launch,
-// a vector one 0.19 %, a taken branch 0.44 % -- ~200 instructions per symbol on the ISA of the pixel loop, 122 of them the symbol decoder.
-// Round 6: the context of a group comes in two supernode forms (8-byte lane words; NARROW 4-byte ones when every property lies inside
+// item above trades scalar instructions for vector ones.  Measured on the 1024 x 4K launch
+// (profiles/r4_instruction_probes.txt): one more scalar instruction per symbol costs 0.37 % of the launch,
+// a vector one 0.19 %, a taken branch 0.44 %.
+// The context of a group comes in two supernode forms (8-byte lane words; NARROW 4-byte ones when every property lies inside
 // 13 bits: kLeafFlagN below) and two leaf forms (31 chances in 64 bytes; COMPACT 16 chances in 32 bytes when the symbols have at most 8 magnitude bits:
-// LeafRegs::mb), chosen per group and carried in the tile record; context areas have the exact size of their context and come from one two-ended arena;
-// the reference loads of a pixel chunk are issued together.  With every wavefront slot busy the launch is bound by what a SIMD ISSUES (LDS-resident
-// supernodes in the dense configuration made a long group 7 % faster and the launch 4.7 % slower: removed), so nothing here may add an instruction
-// to the per-symbol path lightly.
-// The round's last session took instructions OUT (profiles/r6_sq_counters_final.txt: 171 instructions per decoded sample, 81 of them scalar, the scalar issue
-// slots the busier ones): fast_symbol_hw with the exponent decisions on chances 2..9 unrolled and an exit per exponent -- 159 instructions per sample, 71 scalar,
-// the launch 6.36 -> 6.02 s (profiles/r6_unrolled_decoder.txt).
+// LeafRegs::mb), chosen per group and carried in the tile record; context areas have the exact size of their context and come from one
+// two-ended arena; the reference loads of a pixel chunk are issued together.  With every wavefront slot busy the launch is bound by what a SIMD ISSUES,
+// so nothing here may add an instruction to the per-symbol path lightly (DESIGN.md 8 lists the variants that did, and lost).
+// The symbol decoder is hand written (fast_symbol_hw): 159 instructions per decoded sample, 71 of them scalar, the scalar issue slots the busier ones
+// (profiles/r6_sq_counters_final.txt); its unrolled exponent decisions are worth 6.36 -> 6.02 s on the launch (profiles/r6_unrolled_decoder.txt).
 // Three LDS configurations are built: "wide" for a launch alone = 38.9 KB per wave (58 supernodes = 29 KB, 8.4 KB of chunk properties,
 // small state; one wave per SIMD), "wide" for hosts with two batches in flight = 19.7 KB (20 supernodes; exactly two waves per SIMD:
-// fuifgpu_batch_set_in_flight, round 5) and "dense" = 5.7 KB (no supernode slots, 32-pixel chunks;
+// fuifgpu_batch_set_in_flight) and "dense" = 5.7 KB (no supernode slots, 32-pixel chunks;
 // 80 VGPRs: 24 waves per CU, six per SIMD, which fill each other's stalls when tiles outnumber SIMDs).
 // The 16 KB chance transition table is read through L1/L2 instead: its lookups are off the dependency
 // chain thanks to the batched update.
@@ -91,39 +89,23 @@ namespace {
 #endif
 
 constexpr int CH_ZERO = 0, CH_SIGN = 1, CH_EXP = 2, CH_MANT = 16, CH_N = 31;
-// Supernodes (512 B each) of the context tree kept in LDS: the kernel is built twice.
-//   kLdsWide  : 20 supernodes = 10 KB of tree per wavefront (20 KB of LDS with the property rows): exactly TWO wavefronts per SIMD -- for launches with
-//               few tiles (streams without a group index: one tile per image).  Rounds 1-4 kept 58 supernodes (one wavefront per SIMD): a launch
-//               alone was 6 % faster (20.8 against 22.1 s for 1024 x 4K), but a lone wavefront per SIMD is latency-bound and nothing could run beside
-//               it -- with 20, two 1024-picture launches side by side take 24.5 s instead of 41.6 (693 against 408 Mpixels/s; 12 supernodes = three
-//               per SIMD: 662; profiles/r5_overlap_timeline_and_wide_variants.txt)
-//   kLdsDense : no tree in LDS (the root supernode lives in registers), 6 wavefronts per SIMD -- best when
-//               tiles abound (group index): co-resident wavefronts fill each other's stalls and every round
-//               behind the root is one memory fetch (rounds 1-3 kept two slots that served 0.9 % of the rounds)
-#ifndef FUIF_LDS_WIDE
-#define FUIF_LDS_WIDE 20
-#endif
-#ifndef FUIF_LDS_DENSE
-#define FUIF_LDS_DENSE 0   // round 4: the two slots served 0.9 % of the walk rounds (profiles/r2_walk_locality.txt) and cost every round an LDS read, a compare and two branches
-#endif
-// A host that decodes ONE batch at a time (fuifgpu_batch_set_in_flight: 1, the default) gets the wide configuration of rounds 1-4 for its launches with few tiles: 58
-// supernodes in LDS, one wavefront per SIMD -- a launch alone is 6 % faster that way (20.8 against 22.1 s for 1024 x 4K without index); a host that keeps two batches
-// in flight gets the 20-supernode instantiation, whose wavefronts leave room for the other launch's.
-#ifndef FUIF_LDS_WIDE_ALONE
-#define FUIF_LDS_WIDE_ALONE 58
-#endif
-constexpr int kLdsWide = FUIF_LDS_WIDE, kLdsDense = FUIF_LDS_DENSE, kLdsWideAlone = FUIF_LDS_WIDE_ALONE;
-// (Round 6 tried 11 narrow supernodes resident in LDS in the dense configuration as well -- since the children of the top supernodes are numbered by subtree
-// size, the 11 largest second-level supernodes of a long 4K group serve 63-70 % of the rounds behind the root (tools/supernode_packing.py), with the room taken
-// from int16 property rows.  A long group alone got 7 % faster, the 1024-picture launch 4.7 % SLOWER: with every wavefront slot busy the launch is bound by what a
-// SIMD issues, and the six instructions per round cost more than the hidden round trips gave back.  Removed: profiles/r6_variants_lds_records_vs_none.txt.)
-#ifndef FUIF_SIZE_ORDERED
-#define FUIF_SIZE_ORDERED 64   // supernodes (breadth first) whose children are numbered by subtree size; 0 = exit order everywhere
-#endif
-constexpr int kSizeOrdered = FUIF_SIZE_ORDERED;
+// Supernodes (512 B each) of the context tree kept in LDS: the kernel is built in three configurations.
+//   kLdsWideAlone : 58 supernodes in LDS, one wavefront per SIMD -- for launches with few tiles (streams without a group index: one tile per
+//                   image) on a host that decodes ONE batch at a time (fuifgpu_batch_set_in_flight: 1, the default).  A launch alone is 6 % faster
+//                   than with kLdsWide (20.8 against 22.1 s for 1024 x 4K without index).
+//   kLdsWide      : 20 supernodes = 10 KB of tree per wavefront (20 KB of LDS with the property rows): exactly TWO wavefronts per SIMD -- the same
+//                   launches on a host that keeps two batches in flight.  A lone wavefront per SIMD is latency-bound and nothing can run beside it;
+//                   with 20, two 1024-picture launches side by side take 24.5 s instead of 41.6 (693 against 408 Mpixels/s; 12 supernodes = three
+//                   per SIMD: 662; profiles/r5_overlap_timeline_and_wide_variants.txt)
+//   kLdsDense     : no tree in LDS (the root supernode lives in registers), 6 wavefronts per SIMD -- best when tiles abound (group index):
+//                   co-resident wavefronts fill each other's stalls and every round behind the root is one memory fetch.  Slots in LDS do not
+//                   pay here: the launch is bound by what a SIMD issues (profiles/r2_walk_locality.txt, profiles/r6_variants_lds_records_vs_none.txt;
+//                   DESIGN.md 8).
+constexpr int kLdsWide = 20, kLdsDense = 0, kLdsWideAlone = 58;
+constexpr int kSizeOrdered = 64;   // the first 64 supernodes (breadth first) number their children by subtree size, deeper ones in exit order
 constexpr uint32_t kLeafFlag = 0x800000u;
 constexpr uint32_t kSlowFlag = 0x400000u;   // exit leads to a plain tree node (index in the low 16 bits), not to a supernode
-// NARROW supernodes (round 6): 4 bytes per lane instead of 8 -- a supernode is 256 bytes, two cache lines instead of four.  The per-symbol chain of a
+// NARROW supernodes: 4 bytes per lane instead of 8 -- a supernode is 256 bytes, two cache lines instead of four.  The per-symbol chain of a
 // long tile is two dependent memory round trips whose latency grows with everything the ~6000 resident wavefronts keep in flight; halving the supernode
 // record is worth 8-15 % of that chain (tools/ubench_context.hip, profiles/r6_ubench_context_layouts.txt).  Lane word:
 //     [1:0] exit, bits 13..12 | [6:2] property | [19:7] split value (signed, 13 bits) | [31:20] exit, bits 11..0      (a rotation by 20 makes the exit contiguous)
@@ -143,20 +125,25 @@ constexpr int kPropPitch = 33;    // odd pitch: conflict-free column writes / ro
 constexpr int kPropPitchWide = 65;
 // Pixels whose properties are prepared at once (lane = pixel).  The property rows are the largest LDS
 // item; a shorter chunk buys resident wavefronts (the real lever of this kernel: it is issue bound).
-#ifndef FUIF_CHUNK
-#define FUIF_CHUNK 32   // dense configuration; the wide one always prepares 64 pixels at a time
-#endif
-constexpr int kChunkDense = FUIF_CHUNK;
+constexpr int kChunkDense = 32;   // dense configuration; the wide one always prepares 64 pixels at a time
 static_assert(kChunkDense == 64 || kChunkDense == 32 || kChunkDense == 16, "chunk must divide the wavefront");
 // The dense configuration is built for 6 wavefronts per SIMD (80 VGPRs, 32-pixel chunks: 5.8 KB of LDS).  The kernel waits
 // for memory two thirds of the time even with 4 wavefronts per SIMD (a leaf, a supernode and a table line per symbol,
 // profiles/r2_sq_counters_*): measured on 1024 x 4K with the group index, 4 / 5 / 6 / 8 per SIMD = 10.9 / 9.6 / 9.5 /
 // 12.0 s (at 8 the 64-register budget spills in the pixel loop).  The wide configuration (LDS bound: one per SIMD)
 // ignores the bound.
-#ifndef FUIF_WAVES
-#define FUIF_WAVES 6
-#endif
-#define FUIF_OCCUPANCY __attribute__((amdgpu_waves_per_eu(FUIF_WAVES, FUIF_WAVES)))
+constexpr int kWaves = 6;
+#define FUIF_OCCUPANCY __attribute__((amdgpu_waves_per_eu(kWaves, kWaves)))
+// Scratch VGPRs of the hand-written symbol decoder (fast_symbol_hw below): the last registers of the 80-VGPR budget that
+// FUIF_OCCUPANCY sets (512 / 6 rounded down to the allocation granule of 8).  Change one, change the other.
+static_assert(kWaves == 6, "FS_VK .. FS_VA name the top of the 6-wavefront register budget");
+#define FS_VK "v[74:75]"
+#define FS_VK0 "v74"
+#define FS_VK1 "v75"
+#define FS_VBC "v[76:77]"
+#define FS_VB "v76"
+#define FS_VC "v77"
+#define FS_VA "v79"
 
 DEV int rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
 DEV uint32_t rflu(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
@@ -427,7 +414,7 @@ struct LeafRegs {
     int leafv;          // per lane
     uint32_t touched;   // scalar
     uint32_t bits;      // scalar
-    // COMPACT leaves (round 6): a group whose symbols have at most 8 magnitude bits (|diff| <= 255: exponent 0..7) touches only the zero, the sign, 7
+    // COMPACT leaves: a group whose symbols have at most 8 magnitude bits (|diff| <= 255: exponent 0..7) touches only the zero, the sign, 7
     // exponent and 7 mantissa chances of a leaf (symbol.h:167-183), so its leaves are 16 chances = 32 bytes instead of 31 padded to 64: slots 0 zero, 1 sign,
     // 2..8 exponent, 9..15 mantissa.  Only the mantissa's first slot moves (16 -> 9); lanes 16..63 mirror lanes 0..15.  Half the leaf bytes of such
     // a group's context (the larger half of it once the supernodes are narrow): profiles/r6_ubench_context_layouts.txt.
@@ -566,53 +553,12 @@ DEV int fast_symbol(Rac &r, Stream &s, LeafRegs &L, const FastSym &F) {
 #ifndef FUIF_EMU
 // The same symbol decoder as fast_symbol (the C++ above is the specification and what the CPU emulator runs), hand
 // written: hipcc turns the loops with their several exits into ~30 instructions and 4-5 branches per decision (flag
-// registers and copies for every exit); this is 13 per exponent bit and 21 per mantissa bit.  three VGPRs at the top of the register budget are scratch
-// (clobbers).  Per decision: per-lane thresholds range - ((range * chance + 0x800) >> 12) as one 64-bit mad,
-// v_readlane of the lane of the chance in use, scalar compare with `low`; renormalisation out of line.
-// scratch VGPRs = the last ones of the register budget of the build (FUIF_WAVES wavefronts per SIMD): the 64-bit
-// product, the 64-bit rounding constant 0x800 (loaded at the top of the block; 64-bit tuples must be even aligned on
-// gfx950, which an inline-asm "v" operand does not guarantee) and the thresholds
-#if FUIF_WAVES >= 8
-#define FS_VK "v[58:59]"
-#define FS_VK0 "v58"
-#define FS_VK1 "v59"
-#define FS_VBC "v[60:61]"
-#define FS_VB "v60"
-#define FS_VC "v61"
-#define FS_VA "v63"
-#elif FUIF_WAVES == 7
-#define FS_VK "v[66:67]"
-#define FS_VK0 "v66"
-#define FS_VK1 "v67"
-#define FS_VBC "v[68:69]"
-#define FS_VB "v68"
-#define FS_VC "v69"
-#define FS_VA "v71"
-#elif FUIF_WAVES >= 6
-#define FS_VK "v[74:75]"
-#define FS_VK0 "v74"
-#define FS_VK1 "v75"
-#define FS_VBC "v[76:77]"
-#define FS_VB "v76"
-#define FS_VC "v77"
-#define FS_VA "v79"
-#elif FUIF_WAVES == 5
-#define FS_VK "v[90:91]"
-#define FS_VK0 "v90"
-#define FS_VK1 "v91"
-#define FS_VBC "v[92:93]"
-#define FS_VB "v92"
-#define FS_VC "v93"
-#define FS_VA "v95"
-#else
-#define FS_VK "v[122:123]"
-#define FS_VK0 "v122"
-#define FS_VK1 "v123"
-#define FS_VBC "v[124:125]"
-#define FS_VB "v124"
-#define FS_VC "v125"
-#define FS_VA "v127"
-#endif
+// registers and copies for every exit); this is 13 per exponent bit and 21 per mantissa bit.  Per decision: per-lane
+// thresholds range - ((range * chance + 0x800) >> 12) as one 64-bit mad, v_readlane of the lane of the chance in use,
+// scalar compare with `low`; renormalisation out of line.
+// Scratch VGPRs (clobbers; FS_VK .. FS_VA at the top of the register budget, defined next to the occupancy attribute): the
+// 64-bit product, the 64-bit rounding constant 0x800 (loaded at the top of the block; 64-bit tuples must be even aligned on
+// gfx950, which an inline-asm "v" operand does not guarantee) and the thresholds.
 // (the _R forms take the register that holds `range` at that point: the unrolled exponent decisions below leave the threshold they read where it is when it
 // becomes the new range, instead of copying it)
 #define FS_THR_PREP_R(Rr) "v_mad_u64_u32 " FS_VBC ", vcc, " Rr ", %[leafv], " FS_VK "\n\tv_alignbit_b32 " FS_VA ", " FS_VC ", " FS_VB ", 12\n\tv_sub_u32 " FS_VA ", " Rr ", " FS_VA "\n\t"
@@ -629,12 +575,20 @@ DEV int fast_symbol(Rac &r, Stream &s, LeafRegs &L, const FastSym &F) {
 #define FS_RENORM(lbl, back) FS_RENORM_R(lbl, back, "%[R]")
 #define FS_RN_CHECK_R(lbl, back, Rr) "s_cmp_le_u32 " Rr ", 0x10000\n\ts_cbranch_scc1 " lbl "\n" back ":\n\t"
 #define FS_RN_CHECK(lbl, back) FS_RN_CHECK_R(lbl, back, "%[R]")
-// Round 6, last session: the first four exponent decisions (chances 2..5) UNROLLED, each with its own exit that knows e: no chance-index add, loop-end test or
-// taken back-branch per decision, the threshold read stays where it is when it becomes the new range (Rr / Tr swap roles from one decision to the next), and the
-// exit of e = k - 2 runs exactly e mantissa decisions without a counter test and builds the (index, bit) masks from constants.  Needs ilast >= 4 (emax >= 3;
-// chances 5..9 are each tested for existence first); smaller ranges and exponents beyond chance 9 take the loops below, as in rounds 4-5.  The exits of
-// chances 6..9 (exponent 4..7) share one mantissa ladder and the loops' mask code at label 60.  (Six unrolled decisions WITHOUT the existence tests were slower
-// than the loops: the channels whose range ends below chance 7 fell back to them -- profiles/r6_unrolled_decoder.txt.)
+// The exponent decisions on chances 2..9 are unrolled (FS_UEXP), each with its own exit that knows e = k - 2: no chance-index add, loop-end test or taken
+// back-branch per decision.  The unrolled path is entered when ilast >= 4 (emax >= 3): chances 2..4 are decided unconditionally, and each of chances 5..9
+// sits behind its own `ilast` test (a channel's range may end at any of them); a range that ends there leaves through labels 18, 17, 16, 15 or 14 to the
+// exhausted-exponent code at label 40.  Smaller ranges (ilast < 4) take the loops from label 19; an exponent beyond chance 9 continues in the loop at label 20.
+// Registers: a decision reads its threshold into Tr, and on a 0 that threshold IS the new range and stays where it is, so Rr and Tr swap roles from one
+// decision to the next (Rr, Tr = %[R], %[thr] for k = 2, 4, 6, 8 and %[thr], %[R] for k = 3, 5, 7, 9); the paths into the loops that find the range in
+// %[thr] copy it to %[R] (labels 18, 16, 14), and an exit head (FS_EXIT_HEAD) leaves it in %[R].
+// Exits: label 100 + k.  Those of e = 0..3 (102..105) run exactly e mantissa decisions without a counter test and build the (index, bit) masks from
+// constants; those of e = 4..7 (106..109) enter one shared ladder of seven mantissa decisions at the rung of their exponent (204, 205, 206; 109 falls in
+// at the top) and finish in the loops' mask code at label 60.
+// Renormalisation stubs (out of line, label / way back): decision k 110 + k / 120 + k, exit head k 130 + k / 140 + k, the mantissa decisions of exits
+// 103..105 151..156 / 161..166, the shared ladder 171..177 / 181..187.
+// (Six unrolled decisions WITHOUT the existence tests were slower than the loops: the channels whose range ends below chance 7 fell back to them --
+// profiles/r6_unrolled_decoder.txt)
 #define FS_UEXP(k, Rr, Tr, exitl, rnl, backl) \
     FS_THR_PREP_R(Rr) "s_nop 0\n\tv_readlane_b32 " Tr ", " FS_VA ", " k "\n\t" \
     "s_cmp_ge_u32 %[L], " Tr "\n\ts_cbranch_scc1 " exitl "\n\t" \
@@ -655,12 +609,12 @@ DEV int fast_symbol(Rac &r, Stream &s, LeafRegs &L, const FastSym &F) {
     "s_andn2_b32 %[bits], 2, %[sm]\n\ts_or_b32 %[bits], %[bits], %[t1]\n\ts_bitset1_b32 %[bits], " k "\n\t"   /* + the sign decision + the exponent's closing 1 */ \
     "s_bfm_b32 %[t1], " e ", %[mb]\n\ts_or_b32 %[touched], %[t1], " tl "\n\t" \
     "s_bitset1_b32 %[t0], " e "\n\ts_xor_b32 %[t0], %[t0], %[sm]\n\ts_sub_u32 %[res], %[t0], %[sm]\n\t"       /* magnitude = 1 << e | mantissa, signed */
-// (Round 4 measured what one more scalar / vector instruction / taken branch per symbol costs the launch with probe builds of this block: +0.37 % / +0.19 % /
-// +0.44 %, profiles/r4_instruction_probes.txt; the probe macros left the source in round 5 -- `git log -S FUIF_PROBE_S` has them.)
+// (What one more scalar / vector instruction / taken branch per symbol costs the launch was measured with probe builds of this block: +0.37 % / +0.19 % /
+// +0.44 %, profiles/r4_instruction_probes.txt; `git log -S FUIF_PROBE_S` finds the probe macros.)
 // (widx = the stream position inside the window registers `win`: the pixel loop of a chunk whose bytes are all in the stream carries it from symbol to symbol
 // instead of converting to and from Stream::pos around every symbol)
 DEV int fast_symbol_hw_w(Rac &r, uint32_t &widx_io, const uint32_t win, LeafRegs &L, const FastSym &F) {
-    // Round 4 (profiles/r4_instruction_probes.txt: a scalar instruction or a taken branch costs the launch twice a vector one):
+    // A scalar instruction or a taken branch costs the launch twice a vector one (profiles/r4_instruction_probes.txt), hence:
     //   * a decision is `s_sub t, low, thr`: SCC = borrow = (low < thr) = NOT the bit, and three s_cselect / s_addc take it from there
     //     (no compare, no separate subtraction of the selected amount);
     //   * the exponent loop counts the chance index itself (no index add per decision); a one-bit ends it with e < emax, which is
@@ -777,7 +731,7 @@ DEV int fast_symbol_hw_w(Rac &r, uint32_t &widx_io, const uint32_t win, LeafRegs
         FS_EXIT_HEAD("107", "%[thr]", "%[R]", "137f", "147") "s_mov_b32 %[idx], 7\n\t" FS_MINIT("5") "s_branch 205f\n"
         FS_EXIT_HEAD("108", "%[R]", "%[thr]", "138f", "148") "s_mov_b32 %[idx], 8\n\t" FS_MINIT("6") "s_branch 206f\n"
         FS_EXIT_HEAD("109", "%[thr]", "%[R]", "139f", "149") "s_mov_b32 %[idx], 9\n\t" FS_MINIT("7")
-        "207:\n\t" FS_MBIT("177f", "187") "206:\n\t" FS_MBIT("176f", "186") "205:\n\t" FS_MBIT("175f", "185") "204:\n\t" FS_MBIT("174f", "184")
+        FS_MBIT("177f", "187") "206:\n\t" FS_MBIT("176f", "186") "205:\n\t" FS_MBIT("175f", "185") "204:\n\t" FS_MBIT("174f", "184")
         FS_MBIT("173f", "183") FS_MBIT("172f", "182") FS_MBIT("171f", "181") "s_branch 60b\n"
         FS_RENORM_R("116", "126b", "%[thr]") FS_RENORM("117", "127b") FS_RENORM_R("118", "128b", "%[thr]") FS_RENORM("119", "129b")
         FS_RENORM("136", "146b") FS_RENORM("137", "147b") FS_RENORM("138", "148b") FS_RENORM("139", "149b")
@@ -1507,7 +1461,7 @@ __global__ __launch_bounds__(64) FUIF_OCCUPANCY void k_maniac_decode(DecodeParam
         int max_super_here = P.max_super;
         // ONE arena, two bump pointers in one 64-bit word: the tiles that hold >= 1/16 of their picture -- the long per-symbol chains that bound
         // the launch, whose contexts are what the memory system has to keep close -- are packed from the bottom, everything else from the top.
-        // (Rounds 2-5 gave every CU queue its own 64 MiB arena: the hot contexts of a launch lay 512 pages apart instead of ~100; tight
+        // (One 64 MiB arena per CU queue would put the hot contexts of a launch 512 pages apart instead of ~100; tight
         // placement is worth ~6 % of a long tile's per-symbol chain, profiles/r6_ubench_context_layouts.txt.)  Both counters only grow, and an
         // area is granted from ONE atomic snapshot of both, so areas never overlap; a failed request leaves its units unused (the arena
         // was full: the tile is pinned to this wavefront's scratch area).
@@ -1528,9 +1482,9 @@ __global__ __launch_bounds__(64) FUIF_OCCUPANCY void k_maniac_decode(DecodeParam
         // (7n+5)/12 supernodes are enough for n inner nodes (capi.hip), so a build with room for that many never falls to the node-by-node walk
         const uint32_t sn_cap = (7u * ((uint32_t)(tree_size - 1) / 2u) + 5u) / 12u + 1u;
         const bool suspendable_here = sched && kHandOff && (rflu(tile.flags) & kTileSuspendable) && beginc == endc && endc == last_c && nrefs > 0;
-        // Round 6: a suspendable tile whose worst case fits the wavefront's scratch area builds its supernodes THERE and moves them, once their real number
-        // is known, into a context area of exactly that size (rounds 2-5 reserved the worst case: 526 supernode slots for the ~150 a long 4K group has, with
-        // the leaves behind the unused ones -- 2.5x the footprint, and C4's 743 KB per tile ran the arenas dry).  Only trees too large for the scratch
+        // A suspendable tile whose worst case fits the wavefront's scratch area builds its supernodes THERE and moves them, once their real number
+        // is known, into a context area of exactly that size (reserving the worst case would mean 526 supernode slots for the ~150 a long 4K group has,
+        // with the leaves behind the unused ones -- 2.5x the footprint, and C4's 743 KB per tile ran the arenas dry).  Only trees too large for the scratch
         // area (more than ~7000 inner nodes) still reserve their worst case up front.
         bool exact_area = false;
         narrow = narrow_ok && tree_size <= kNarrowMaxNodes && (int)sn_cap <= P.max_super;
@@ -1811,8 +1765,8 @@ __global__ __launch_bounds__(64) FUIF_OCCUPANCY void k_maniac_decode(DecodeParam
                                     cp[2 * k] = iabs(v); cp[2 * k + 1] = slog(v);
                                 }
                                 // The reference samples of this pixel: every load is a memory round trip (another tile's plane, read past the L1), so the
-                                // loads of up to 6 references -- what the default options give -- are ISSUED TOGETHER and consumed afterwards.  (Rounds 1-5
-                                // had one `if (k < nrefs)` block per reference: a uniform branch between two loads, which hipcc does not hoist a load
+                                // loads of up to 6 references -- what the default options give -- are ISSUED TOGETHER and consumed afterwards.  (One
+                                // `if (k < nrefs)` block per reference would put a uniform branch between two loads, which hipcc does not hoist a load
                                 // across -- six round trips one after the other, 7200 cycles per 32-pixel chunk on the long 4K groups,
                                 // profiles/r6_phases_by_channel_narrow.txt.)  A slot beyond nrefs reads reference 0 again and is dropped.
                                 auto ref_sample = [&](int k) -> int {

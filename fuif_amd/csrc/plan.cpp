@@ -711,7 +711,7 @@ struct Builder {
         }
     }
 
-    // Peephole on the flat schedule (round 5): the dequantisation of a JPEG-transcoded stream (quantize.h:32-49: every coefficient plane times its q)
+    // Peephole on the flat schedule: the dequantisation of a JPEG-transcoded stream (quantize.h:32-49: every coefficient plane times its q)
     // runs over 192 planes, 189 of which -- the AC coefficient planes -- are coded planes nobody touches before and that exactly one iDCT reads
     // afterwards.  For those the product is folded into the iDCT's load: the iDCT's source entry becomes BUF_COEF16Q (the int16 sample in the
     // coefficient slab times ChannelMeta::q of the plane's channel) and the plane leaves the QUANT op's list -- no widened int32 copy, no in-place
@@ -789,7 +789,7 @@ struct Builder {
         }
     }
 
-    // Peephole on the flat schedule (round 5): [UPSAMPLE 2x2 -> Cb, UPSAMPLE 2x2 -> Cr, YCBCR(Y, Cb, Cr)], the way every 4:2:0 JPEG-transcoded chain
+    // Peephole on the flat schedule: [UPSAMPLE 2x2 -> Cb, UPSAMPLE 2x2 -> Cr, YCBCR(Y, Cb, Cr)], the way every 4:2:0 JPEG-transcoded chain
     // ends (subsample.h:90-115, ycbcr.h:49-60), becomes ONE op: the full-size Cb / Cr planes are never written and read back (283 -> 150 MB of plane
     // traffic per 4K picture for these three ops).  The chroma planes may be larger than the Y plane (block padding): their samples outside the
     // colour transform's region get the upsampled value and the final clamp, as the separate ops + image.cpp:107-113 leave them.
@@ -963,7 +963,7 @@ struct Builder {
             bool range_ok = (lk == OP_YCBCR) || (lk == OP_YCOCG && plan.minval == 0);
             // (the colour transforms clamp what they write -- the p0 x p1 samples of the first channel's geometry.  A chroma plane that is larger
             // than that, block padding of a subsampled JPEG whose size is no multiple of 16, keeps samples they never touch: those need the final
-            // clamp of image.cpp:107-113 like any other -- round 5; rounds 1-4 skipped it: no stream at hand leaves those samples out of range, so no fixture noticed)
+            // clamp of image.cpp:107-113 like any other; no stream at hand leaves those samples out of range, so no fixture would notice its absence)
             if (range_ok && lw >= 0 && ((int64_t)planes[pl].w != (int64_t)ops[lw].p0 || (int64_t)planes[pl].h != (int64_t)ops[lw].p1)) range_ok = false;
             if (range_ok) continue;
             if (lw >= 0 && planes[pl].birth == lw &&

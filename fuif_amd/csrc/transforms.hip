@@ -52,10 +52,7 @@ DEV int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); 
 
 // ---------------------------------------------------------------------------------------------
 // vertical unsqueeze: avg (w x h1) + residual (w x h2) -> out (w x (h1+h2)), h1-h2 in {0,1}
-#ifndef FUIF_VS_STEP
-#define FUIF_VS_STEP 8
-#endif
-constexpr int VS_STEP = FUIF_VS_STEP;
+constexpr int VS_STEP = 8;
 template <typename TR>
 __global__ __launch_bounds__(256) void k_inv_vsqueeze(Bases b, PlaneRef pa, PlaneRef pr, PlaneRef po, int clamp, int lo, int hi) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
@@ -181,10 +178,7 @@ __global__ __launch_bounds__(256) void k_inv_hsqueeze_rows(Bases b, PlaneRef pa,
 // 2*HL_P outputs back into LDS (the output tile aliases the input tiles: every lane holds its inputs in registers by then)
 // and the tile is written out 16 lanes per 256-byte output row.  Row pitches of 36 / 68 words keep the b128 LDS accesses of
 // 16 neighbouring lanes on different banks.
-#ifndef FUIF_HL_P
-#define FUIF_HL_P 32
-#endif
-constexpr int HL_P = FUIF_HL_P;            // pairs per tile row: 32 (128-byte input segments, 18 KB of LDS) or 16 (64-byte segments, 9 KB)
+constexpr int HL_P = 32;                   // pairs per tile row: 128-byte input segments, 18 KB of LDS
 constexpr int HL_IN_LANES = HL_P / 4;      // lanes that fetch one input row segment (16 bytes each)
 constexpr int HL_IN_STEPS = HL_P / 4;      // load instructions per input tile: 64 rows / (64 / HL_IN_LANES) rows per instruction
 constexpr int HL_OUT_LANES = HL_P / 2, HL_OUT_STEPS = HL_P / 2;

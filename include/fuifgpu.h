@@ -17,8 +17,8 @@
 extern "C" {
 #endif
 
-#define FUIFGPU_ABI_VERSION 3   /* 2 (round 4): fuifgpu_encode_options starts with struct_size; sibling batches freeze the launch resources.
-                                 * 3 (rounds 5-6): every fuifgpu_batch_* call runs on the batch's own device (the caller's is restored on return);
+#define FUIFGPU_ABI_VERSION 3   /* 2: fuifgpu_encode_options starts with struct_size; sibling batches freeze the launch resources.
+                                 * 3: every fuifgpu_batch_* call runs on the batch's own device (the caller's is restored on return);
                                  *   the device / peer-copy / checksum / in-flight entry points exist; fuifgpu_batch_create reads FUIFGPU_IN_FLIGHT.
                                  *   A host checks fuifgpu_abi_version() >= the version whose entry points it binds before looking them up. */
 
@@ -207,7 +207,7 @@ int fuifgpu_batch_set_group_parallel(fuifgpu_batch *batch, int enable);
  * The reference decodes one file at a time (fuif.cpp:213-233); no counterpart. */
 int fuifgpu_batch_set_in_flight(fuifgpu_batch *batch, int n_batches);
 
-/* ---- several GPUs of one node (round 5) ---------------------------------------------------------------------
+/* ---- several GPUs of one node -----------------------------------------------------------------------------
  * The reference decodes file after file on one core (fuif.cpp:213-233: fuif_decode_file + undo_transforms per file); a batch of
  * independent images shards across the GPUs of a node with no data-path exchange.  Inside ONE process the unit is
  * the calling thread's current device, as in HIP: fuifgpu_set_device() selects it, a batch lives on the device that was current when
@@ -284,7 +284,7 @@ int fuifgpu_fwd_vsqueeze(const int32_t *in, int w, int h, int32_t *avg, int32_t 
 typedef struct {
     uint32_t struct_size;   /* = sizeof(fuifgpu_encode_options) of the CALLER's header.  The library reads that many bytes and takes
                                every field behind them as 0, so the struct can grow at its end without breaking callers built
-                               against an older header (ABI 2, round 4: round 3 appended gpu_entropy to the unversioned struct and a
+                               against an older header (ABI 2: an earlier build appended gpu_entropy to the unversioned struct, and a
                                caller built before that had 4 bytes read past its object).  0 or a size that is not a multiple of
                                4 is FUIFGPU_E_ARG. */
     int32_t ycocg;          /* 1: YCoCg when nch >= 3 (CLI default) */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Throughput of k_maniac_decode against resident wavefronts per SIMD and LDS-resident supernodes.
+"""Throughput of k_maniac_decode on launches of n_streams streams (the workload tools/pmc_sq.sh counts).
 
-  FUIF_AMD_LIB=<lib built with -DFUIF_LDS_SUPER=k> python tools/occupancy_probe.py n_streams[,n..] [w h] [seq]
+  [FUIF_AMD_LIB=<a library built by tools/build_variant.sh>] python tools/occupancy_probe.py n_streams[,n..] [w h] [seq]
 one launch over n_streams streams (8 distinct images, replicated); `seq` ignores the group index."""
 import os
 import sys
