@@ -42,19 +42,18 @@ struct fuifgpu_batch {
     int scratch_waves = 0;            // wavefronts d_scratch is sized for
     int max_waves[3] = {0, 0, 0};     // resident wavefronts the device holds in the kernel configurations: wide for two batches in flight / dense / wide for a launch alone
     int in_flight = 1;                // batches the host keeps in flight on this device (fuifgpu_batch_set_in_flight): picks the wide configuration
-    int n_waves = 0, dense = 0, cfg = 1;   // persistent wavefronts and configuration (index into max_waves) of the next decode launch
+    int n_waves = 0, cfg = 1;         // persistent wavefronts and configuration (index into max_waves) of the next decode launch
     bool group_parallel = true;       // use group indices (index.cpp) when streams carry them
     Tile *d_tiles = nullptr;
     int tiles_cap = 0, n_tiles = 0;
     uint32_t *d_progress = nullptr, *d_group_start = nullptr;
-    // scheduler state of the entropy kernel (maniac_decode.h), zeroed per launch, and the queue / image layout tables
+    // scheduler state of the entropy kernel (maniac_decode.h: sched_layout), zeroed per launch, and the queue / image tables (queue_layout)
     uint32_t *d_sched = nullptr, *d_layout = nullptr;
     size_t sched_words = 0, layout_cap = 0;
     int sched = 0, n_queues = 1, waves_per_simd = 4;
     uint8_t *d_ctx = nullptr;         // context areas of suspendable tiles (sched == 1)
     size_t ctx_bytes = 0;
     uint32_t ctx_units_per_queue = 0;
-    std::vector<Tile> tiles;
     int max_nodes = kMaxNodes;
     coef_t *d_coef = nullptr;         // int16 samples: what the entropy kernel writes (fuifgpu_internal.h)
     int32_t *d_out = nullptr, *d_tmp = nullptr;
@@ -96,6 +95,19 @@ static int fail_msg(int code, const char *what) {
         hipError_t e__ = (call);                          \
         if (e__ != hipSuccess) return hip_fail(e__, #call); \
     } while (0)
+
+// Grows a device buffer to `need` units of `unit` bytes (the contents are not kept; it never shrinks).  A failed allocation leaves a null
+// pointer with capacity 0, which is what fuifgpu_batch_destroy and the next call expect.  sync_first: the device may still be using the old buffer.
+template <typename T, typename N>
+static int grow(T *&ptr, N &cap, N need, size_t unit = sizeof(T), bool sync_first = false) {
+    if (need <= cap) return FUIFGPU_OK;
+    if (sync_first) HIPCHK(hipDeviceSynchronize());
+    hipFree(ptr); ptr = nullptr; cap = 0;
+    HIPCHK(hipMalloc((void **)&ptr, unit * (size_t)need));
+    cap = need;
+    return FUIFGPU_OK;
+}
+#define OKCHK(call) do { const int rc__ = (call); if (rc__ != FUIFGPU_OK) return rc__; } while (0)
 
 namespace fuifgpu {
 // Supernodes a wavefront's scratch area holds.  A tree of n inner nodes needs at most (7n+5)/12 of them
@@ -312,36 +324,30 @@ int fuifgpu_batch_create(const fuifgpu_plan *plan, int n_images, size_t blob_cap
     return batch_create_impl(plan->plan, n_images, blob_capacity_bytes, coef_ext, out_ext, tmp_images, nullptr, out);
 }
 
+// The context arena a batch may have for `images` images: 16 MiB each (see reserve_launch_buffers), never more than half of the device
+// memory that is free (counting what the batch holds already), a multiple of the 256-byte unit
+static size_t ctx_arena_budget(const fuifgpu_batch *b, size_t images) {
+    size_t per_image = 16u << 20;
+    if (const char *e = getenv("FUIFGPU_CTX_MB")) per_image = (size_t)std::max(1, atoi(e)) << 20;
+    if (const char *e = getenv("FUIFGPU_CTX_KB")) per_image = (size_t)std::max(0, atoi(e)) << 10;   // tests: arenas that run out (pinned tiles)
+    size_t want = per_image * images, free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) want = std::min(want, (free_b + b->ctx_bytes) / 2);
+    return want / 256 * 256;
+}
+// DecodeParams::ctx_units_per_queue of an arena shared out over n_queues; the whole arena stays below 2^32 units (TileRec::ctx, the halves of ctx_used)
+static uint32_t ctx_units_per_queue(size_t arena_bytes, int n_queues) {
+    const size_t q = (size_t)std::max(n_queues, 1);
+    return (uint32_t)std::min(arena_bytes / q / 256, (size_t)0xFFFFFF00u / q);
+}
 // The launch resources a sibling borrows must not move while it may be decoding: the documented pipeline runs an upload into one
 // batch on a host thread while the other batch decodes.  When the first sibling is created the primary's decoder scratch and
 // context arenas are therefore sized ONCE for the worst case -- as many wavefronts as the device holds (or the batch can ever
 // have tiles), arenas for a full batch -- and are never reallocated while a sibling exists (fuifgpu_batch_upload clamps to them).
-static size_t ctx_bytes_per_image() {
-    size_t per_image = 16u << 20;
-    if (const char *e = getenv("FUIFGPU_CTX_MB")) per_image = (size_t)std::max(1, atoi(e)) << 20;
-    if (const char *e = getenv("FUIFGPU_CTX_KB")) per_image = (size_t)std::max(0, atoi(e)) << 10;   // tests: arenas that run out (pinned tiles)
-    return per_image;
-}
 static int freeze_launch_resources(fuifgpu_batch *b) {
     const int64_t cap = std::max(std::max(b->max_waves[0], b->max_waves[1]), b->max_waves[2]);
     const int waves = (int)std::max<int64_t>(1, std::min<int64_t>(cap, (int64_t)b->n * std::max<int64_t>((int64_t)b->plan.coded.size(), 1)));
-    if (waves > b->scratch_waves) {
-        HIPCHK(hipDeviceSynchronize());
-        hipFree(b->d_scratch); b->d_scratch = nullptr; b->scratch_waves = 0;
-        HIPCHK(hipMalloc((void **)&b->d_scratch, b->scratch_stride * (size_t)waves));
-        b->scratch_waves = waves;
-    }
-    size_t need = ctx_bytes_per_image() * (size_t)b->n;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) need = std::min(need, (free_b + b->ctx_bytes) / 2);
-    need = need / 256 * 256;
-    if (need > b->ctx_bytes) {
-        HIPCHK(hipDeviceSynchronize());
-        hipFree(b->d_ctx); b->d_ctx = nullptr; b->ctx_bytes = 0;
-        HIPCHK(hipMalloc((void **)&b->d_ctx, std::max<size_t>(need, 256)));
-        b->ctx_bytes = need;
-    }
-    return FUIFGPU_OK;
+    OKCHK(grow(b->d_scratch, b->scratch_waves, waves, b->scratch_stride, true));
+    return grow(b->d_ctx, b->ctx_bytes, ctx_arena_budget(b, (size_t)b->n), 1, true);
 }
 
 int fuifgpu_batch_create_streaming(const fuifgpu_plan *plan, int n_images, size_t blob_capacity_bytes, int tmp_images, fuifgpu_batch **out) {
@@ -352,17 +358,15 @@ int fuifgpu_batch_create_streaming(const fuifgpu_plan *plan, int n_images, size_
 int fuifgpu_batch_create_sibling(fuifgpu_batch *primary, size_t blob_capacity_bytes, fuifgpu_batch **out) {
     if (!primary || primary->share || primary->no_out) return FUIFGPU_E_ARG;
     ON_BATCH_DEVICE(primary);
-    if (primary->siblings.empty()) { const int frc = freeze_launch_resources(primary); if (frc != FUIFGPU_OK) return frc; }
+    if (primary->siblings.empty()) OKCHK(freeze_launch_resources(primary));
     const int rc = batch_create_impl(primary->plan, primary->n, blob_capacity_bytes, primary->d_coef, primary->d_out, primary->tmp_images, primary, out);
     if (rc == FUIFGPU_OK) primary->siblings.push_back(*out);
     return rc;
 }
 
-int fuifgpu_batch_upload(fuifgpu_batch *b, const uint8_t *const *blobs, const size_t *sizes, int n_images, int preview, void *stream) {
-    ON_BATCH_DEVICE(b);
-    if (!b || !blobs || !sizes || n_images < 1 || n_images > b->n || preview < -1 || preview > 4) return FUIFGPU_E_ARG;
-    if (b->orphan) { g_last_error = "sibling batch: its primary has been destroyed"; return FUIFGPU_E_ARG; }
-    hipStream_t st = (hipStream_t)stream;
+// fuifgpu_batch_upload, step 1: the streams into d_blobs and their jobs into d_jobs; per distinct stream its tiles' first bytes / channels
+static int stage_streams(fuifgpu_batch *b, const uint8_t *const *blobs, const size_t *sizes, int n_images, int preview, hipStream_t st,
+                         std::vector<std::vector<GroupEntry>> &groups, std::vector<int> &group_of) {
     b->jobs.assign(n_images, StreamJob{});
     size_t off = 0;
     Plan tmp;
@@ -370,8 +374,7 @@ int fuifgpu_batch_upload(fuifgpu_batch *b, const uint8_t *const *blobs, const si
     // 1024-image batch built from K distinct streams moves K streams over PCIe, not 1024.
     std::vector<std::pair<const uint8_t *, int>> seen;
     const int nch = (int)b->plan.coded.size();
-    std::vector<std::vector<GroupEntry>> groups;   // per distinct stream: its tiles' first bytes / channels
-    std::vector<int> group_of(n_images, -1);
+    group_of.assign(n_images, -1);
     HIPCHK(hipStreamSynchronize(st));
     for (int i = 0; i < n_images; i++) {
         if (sizes[i] > 0xFFFFFFF0ull) return FUIFGPU_E_ARG;
@@ -405,15 +408,28 @@ int fuifgpu_batch_upload(fuifgpu_batch *b, const uint8_t *const *blobs, const si
         off += padded;
     }
     HIPCHK(hipMemcpyAsync(b->d_jobs, b->jobs.data(), sizeof(StreamJob) * n_images, hipMemcpyHostToDevice, st));
-    // Work list.  Which configuration runs is known from the tile count alone: more tiles than the wide configuration
+    return FUIFGPU_OK;
+}
+
+// fuifgpu_batch_upload, step 2: which configuration launches and the work list it walks.  Host arithmetic only.
+struct WorkList {
+    int cfg = 1, n_waves = 0, sched = 0, n_queues = 1;
+    std::vector<Tile> tiles;
+    std::vector<uint32_t> layout;   // sched: the words of queue_layout() (maniac_decode.h)
+};
+static WorkList plan_work_list(const Plan &plan, const std::vector<std::vector<GroupEntry>> &groups, const std::vector<int> &group_of, const size_t *sizes,
+                               const int *max_waves, int waves_per_simd, int in_flight, bool group_order) {
+    WorkList wl;
+    const int n_images = (int)group_of.size(), nch = (int)plan.coded.size();
+    // Which configuration runs is known from the tile count alone: more tiles than the wide configuration
     // has wavefronts -> dense (4 wavefronts per SIMD).
     size_t total_tiles = 0, deepest = 0;
     for (int i = 0; i < n_images; i++) total_tiles += groups[group_of[i]].size();
     for (auto &g : groups) deepest = std::max(deepest, g.size());
-    const int wide_cfg = b->in_flight > 1 ? 0 : 2;      // a host with two batches in flight leaves room for the other launch's wavefronts (20 LDS supernodes: two per SIMD)
-    b->dense = (int64_t)total_tiles > b->max_waves[wide_cfg] ? 1 : 0;
-    b->cfg = b->dense ? 1 : wide_cfg;
-    b->n_waves = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)total_tiles, b->max_waves[b->cfg]));
+    const int wide_cfg = in_flight > 1 ? 0 : 2;      // a host with two batches in flight leaves room for the other launch's wavefronts (20 LDS supernodes: two per SIMD)
+    const bool dense = (int64_t)total_tiles > max_waves[wide_cfg];
+    wl.cfg = dense ? 1 : wide_cfg;
+    wl.n_waves = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)total_tiles, max_waves[wl.cfg]));
     // an image whose every tile holds exactly one non-empty channel (one single-channel group per tile) may have its tiles suspended
     std::vector<char> suspendable(groups.size(), 0);
     for (size_t gi = 0; gi < groups.size(); gi++) {
@@ -422,13 +438,13 @@ int fuifgpu_batch_upload(fuifgpu_batch *b, const uint8_t *const *blobs, const si
         for (size_t k = 0; k < g.size() && ok; k++) {
             const int first = k == 0 ? 0 : g[k].first_channel, last = k + 1 < g.size() ? g[k + 1].first_channel - 1 : nch - 1;
             int nonempty = 0;
-            for (int c = first; c <= last; c++) nonempty += (int64_t)b->plan.coded[c].w * b->plan.coded[c].h > 0 ? 1 : 0;
+            for (int c = first; c <= last; c++) nonempty += (int64_t)plan.coded[c].w * plan.coded[c].h > 0 ? 1 : 0;
             ok = nonempty <= 1;
         }
         suspendable[gi] = ok ? 1 : 0;
     }
     int64_t image_samples = 0;
-    for (int c = 0; c < nch; c++) image_samples += (int64_t)b->plan.coded[c].w * b->plan.coded[c].h;
+    for (int c = 0; c < nch; c++) image_samples += (int64_t)plan.coded[c].w * plan.coded[c].h;
     auto push_tile = [&](int i, size_t k) {
         const std::vector<GroupEntry> &g = groups[group_of[i]];
         if (k >= g.size()) return;
@@ -442,116 +458,97 @@ int fuifgpu_batch_upload(fuifgpu_batch *b, const uint8_t *const *blobs, const si
         // size class = floor(log2(samples of the image / samples of the tile)): the few tiles that hold most of an image are its
         // critical path (one range coder each), the kernel runs them at a higher wavefront priority
         int64_t mine = 0;
-        for (int c = (int)t.first_channel; c <= (int)t.last_channel; c++) mine += (int64_t)b->plan.coded[c].w * b->plan.coded[c].h;
+        for (int c = (int)t.first_channel; c <= (int)t.last_channel; c++) mine += (int64_t)plan.coded[c].w * plan.coded[c].h;
         uint32_t cls = 15;
         if (mine > 0) { cls = 0; while (cls < 15 && (mine << (cls + 1)) <= image_samples) cls++; }
         t.flags |= cls << kTileSizeClassShift;
-        b->tiles.push_back(t);
+        wl.tiles.push_back(t);
     };
     // Dense launches with more tiles than wavefronts use the context scheduler (maniac_decode.h, sched == 1): tiles image by
     // image in stream order, images dealt to one queue per CU, a tile that would wait for another tile's rows is
     // suspended instead of holding its wavefront (measured on 1024 x 4K: a quarter of all wavefront time was spent in
     // such waits, profiles/r2_tile_timeline_baseline.txt).  Otherwise -- and with FUIFGPU_TILE_ORDER=group, a diagnostic
     // -- one group-major list: tile k of every image before tile k+1 of any.
-    const char *ord = getenv("FUIFGPU_TILE_ORDER");
-    b->sched = b->dense && (int64_t)total_tiles > b->n_waves && !(ord && !strcmp(ord, "group")) ? 1 : 0;
-    b->tiles.clear();
-    std::vector<uint32_t> layout;   // sched: q_img_begin [Q+1] | q_images [n] | img_tile_begin [n+1]
-    if (!b->sched) {
-        b->n_queues = 1;
+    wl.sched = dense && (int64_t)total_tiles > wl.n_waves && !group_order ? 1 : 0;
+    if (!wl.sched) {
         for (size_t k = 0; k < deepest; k++)
             for (int i = 0; i < n_images; i++) push_tile(i, k);
-    } else {
-        const int waves_per_cu = 4 * std::max(1, b->waves_per_simd);
-        b->n_queues = std::max(1, std::min(n_images, b->n_waves / waves_per_cu));
-        const int Q = b->n_queues;
-        layout.resize((size_t)Q + 1 + n_images + n_images + 1);
-        uint32_t *qib = layout.data(), *qim = qib + Q + 1, *itb = qim + n_images;
-        // Images are dealt to the queues longest stream first, back and forth (0..Q-1, Q-1..0, ...): every queue gets the same
-        // number of images and a similar number of bytes.  Dealing them in caller order put the copies of one picture on
-        // one CU (a batch of K pictures replicated, K dividing Q), and the CUs holding the longest pictures finished 1.3 s
-        // after the median one (profiles/r2_priority_and_balance.txt); the stream length is the best predictor of the
-        // decoding time the host has.
-        std::vector<int> by_size(n_images);
-        for (int i = 0; i < n_images; i++) by_size[i] = i;
-        std::stable_sort(by_size.begin(), by_size.end(), [&](int x, int y) { return sizes[x] > sizes[y]; });
-        std::vector<std::vector<uint32_t>> dealt(Q);
-        for (int k = 0; k < n_images; k++) {
-            const int round = k / Q, at = k % Q;
-            dealt[(round & 1) ? Q - 1 - at : at].push_back((uint32_t)by_size[k]);
-        }
-        uint32_t pos = 0;
-        for (int q = 0; q < Q; q++) {
-            qib[q] = pos;
-            std::sort(dealt[q].begin(), dealt[q].end());   // caller order inside a queue
-            for (uint32_t i : dealt[q]) qim[pos++] = i;
-        }
-        qib[Q] = pos;
-        for (int i = 0; i < n_images; i++) {
-            itb[i] = (uint32_t)b->tiles.size();
-            for (size_t k = 0; k < groups[group_of[i]].size(); k++) push_tile(i, k);
-        }
-        itb[n_images] = (uint32_t)b->tiles.size();
+        return wl;
     }
-    b->n_tiles = (int)b->tiles.size();
-    {
-        // scheduler state, zeroed before every launch: q_head | done_total | statistics | started_total | heartbeat | cu claim table |
-        // cu_alive | cu_live | cu_foreign | img_next | img_done | ctx_used | tile records
-        const size_t words = 24 + (2 * 4096 + 1) + 3 * 4096 + 4 * 4096 + 2 * (size_t)n_images + (size_t)b->n_queues + (b->sched ? (size_t)b->n_tiles * (sizeof(TileRec) / 4) : 0);
-        if (words > b->sched_words) {
-            hipFree(b->d_sched); b->d_sched = nullptr; b->sched_words = 0;
-            HIPCHK(hipMalloc((void **)&b->d_sched, words * 4));
-            b->sched_words = words;
-        }
-        if (layout.size() > b->layout_cap) {
-            hipFree(b->d_layout); b->d_layout = nullptr; b->layout_cap = 0;
-            HIPCHK(hipMalloc((void **)&b->d_layout, layout.size() * 4));
-            b->layout_cap = layout.size();
-        }
-        if (!layout.empty()) HIPCHK(hipMemcpyAsync(b->d_layout, layout.data(), layout.size() * 4, hipMemcpyHostToDevice, st));
-        if (b->sched && !b->share) {
-            // Context arenas: a suspendable tile keeps its supernodes and leaf chances in its image's queue arena (bump
-            // allocation inside a launch).  16 MiB per image covers trees of ~2000 nodes on every tile of a 61-tile image
-            // three times over (FUIFGPU_CTX_MB overrides); a tile that finds the arena full is simply not suspendable.
-            const size_t per_image = ctx_bytes_per_image();
-            const size_t images_per_queue = ((size_t)n_images + b->n_queues - 1) / b->n_queues;
-            size_t per_queue = per_image * images_per_queue;
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                const size_t budget = (free_b + b->ctx_bytes) / 2;   // never more than half of what is left
-                if (per_queue * (size_t)b->n_queues > budget) per_queue = budget / (size_t)b->n_queues;
-            }
-            // a primary with siblings never moves its arenas (a sibling may be decoding out of them right now): it lives with what
-            // fuifgpu_batch_create_sibling froze
-            if (!b->siblings.empty()) per_queue = std::min(per_queue, b->ctx_bytes / (size_t)b->n_queues);
-            per_queue = std::min<size_t>(per_queue / 256 * 256, (size_t)0xFFFFFF00u / (size_t)b->n_queues * 256);
-            b->ctx_units_per_queue = (uint32_t)(per_queue / 256);
-            const size_t need = per_queue * (size_t)b->n_queues;
-            if (need > b->ctx_bytes) {
-                hipFree(b->d_ctx); b->d_ctx = nullptr; b->ctx_bytes = 0;
-                HIPCHK(hipMalloc((void **)&b->d_ctx, std::max<size_t>(need, 256)));
-                b->ctx_bytes = need;
-            }
-        }
-        HIPCHK(hipStreamSynchronize(st));  // layout is a local
+    const int waves_per_cu = (int)kSimdsPerCu * std::max(1, waves_per_simd);
+    const int Q = wl.n_queues = std::max(1, std::min(n_images, wl.n_waves / waves_per_cu));
+    const QueueLayout L = queue_layout(Q, n_images);
+    wl.layout.resize(L.words);
+    uint32_t *qib = wl.layout.data() + L.q_img_begin, *qim = wl.layout.data() + L.q_images, *itb = wl.layout.data() + L.img_tile_begin;
+    // Images are dealt to the queues longest stream first, back and forth (0..Q-1, Q-1..0, ...): every queue gets the same
+    // number of images and a similar number of bytes.  Dealing them in caller order put the copies of one picture on
+    // one CU (a batch of K pictures replicated, K dividing Q), and the CUs holding the longest pictures finished 1.3 s
+    // after the median one (profiles/r2_priority_and_balance.txt); the stream length is the best predictor of the
+    // decoding time the host has.
+    std::vector<int> by_size(n_images);
+    for (int i = 0; i < n_images; i++) by_size[i] = i;
+    std::stable_sort(by_size.begin(), by_size.end(), [&](int x, int y) { return sizes[x] > sizes[y]; });
+    std::vector<std::vector<uint32_t>> dealt(Q);
+    for (int k = 0; k < n_images; k++) {
+        const int round = k / Q, at = k % Q;
+        dealt[(round & 1) ? Q - 1 - at : at].push_back((uint32_t)by_size[k]);
     }
-    if (b->n_tiles > b->tiles_cap) {
-        hipFree(b->d_tiles); b->d_tiles = nullptr; b->tiles_cap = 0;
-        HIPCHK(hipMalloc((void **)&b->d_tiles, sizeof(Tile) * (size_t)b->n_tiles));
-        b->tiles_cap = b->n_tiles;
+    uint32_t pos = 0;
+    for (int q = 0; q < Q; q++) {
+        qib[q] = pos;
+        std::sort(dealt[q].begin(), dealt[q].end());   // caller order inside a queue
+        for (uint32_t i : dealt[q]) qim[pos++] = i;
     }
-    if (b->n_tiles) HIPCHK(hipMemcpyAsync(b->d_tiles, b->tiles.data(), sizeof(Tile) * (size_t)b->n_tiles, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));  // b->tiles / b->jobs may be rebuilt by the next upload
+    qib[Q] = pos;
+    for (int i = 0; i < n_images; i++) {
+        itb[i] = (uint32_t)wl.tiles.size();
+        for (size_t k = 0; k < groups[group_of[i]].size(); k++) push_tile(i, k);
+    }
+    itb[n_images] = (uint32_t)wl.tiles.size();
+    return wl;
+}
+
+// fuifgpu_batch_upload, step 3: device memory for the launch the batch now describes (n_tiles, n_waves, sched, n_queues)
+static int reserve_launch_buffers(fuifgpu_batch *b, int n_images, size_t layout_words) {
+    OKCHK(grow(b->d_sched, b->sched_words, sched_layout(n_images, b->n_queues, b->sched ? b->n_tiles : 0)));
+    OKCHK(grow(b->d_layout, b->layout_cap, layout_words));
+    OKCHK(grow(b->d_tiles, b->tiles_cap, b->n_tiles));
+    if (b->sched && !b->share) {
+        // Context arenas: a suspendable tile keeps its supernodes and leaf chances in its image's queue arena (bump
+        // allocation inside a launch).  16 MiB per image covers trees of ~2000 nodes on every tile of a 61-tile image
+        // three times over (FUIFGPU_CTX_MB overrides); a tile that finds the arena full is simply not suspendable.
+        const size_t images_per_queue = ((size_t)n_images + b->n_queues - 1) / b->n_queues;
+        size_t arena = ctx_arena_budget(b, images_per_queue * (size_t)b->n_queues);
+        // a primary with siblings never moves its arenas (a sibling may be decoding out of them right now): it lives with what
+        // fuifgpu_batch_create_sibling froze
+        if (!b->siblings.empty()) arena = std::min(arena, b->ctx_bytes);
+        b->ctx_units_per_queue = ctx_units_per_queue(arena, b->n_queues);
+        OKCHK(grow(b->d_ctx, b->ctx_bytes, (size_t)b->ctx_units_per_queue * 256 * (size_t)b->n_queues));
+    }
     // one persistent wavefront per tile up to what the device holds at once; each owns a scratch area
-    if (b->share) {
-        // a sibling launches with the primary's decoder scratch, sized for the device's wavefront capacity when the sibling was created
+    if (b->share) {   // a sibling launches with the primary's decoder scratch, sized for the device's wavefront capacity when the sibling was created
         if (b->n_waves > b->share->scratch_waves) { g_last_error = "sibling batch: more wavefronts than the primary's decoder scratch was sized for"; return FUIFGPU_E_ARG; }
-    } else if (b->n_waves > b->scratch_waves) {
-        if (!b->siblings.empty()) { g_last_error = "primary batch with siblings: decoder scratch cannot grow (internal sizing error)"; return FUIFGPU_E_ARG; }
-        hipFree(b->d_scratch); b->d_scratch = nullptr; b->scratch_waves = 0;
-        HIPCHK(hipMalloc((void **)&b->d_scratch, b->scratch_stride * (size_t)b->n_waves));
-        b->scratch_waves = b->n_waves;
+        return FUIFGPU_OK;
     }
+    if (b->n_waves > b->scratch_waves && !b->siblings.empty()) { g_last_error = "primary batch with siblings: decoder scratch cannot grow (internal sizing error)"; return FUIFGPU_E_ARG; }
+    return grow(b->d_scratch, b->scratch_waves, b->n_waves, b->scratch_stride);
+}
+
+int fuifgpu_batch_upload(fuifgpu_batch *b, const uint8_t *const *blobs, const size_t *sizes, int n_images, int preview, void *stream) {
+    ON_BATCH_DEVICE(b);
+    if (!b || !blobs || !sizes || n_images < 1 || n_images > b->n || preview < -1 || preview > 4) return FUIFGPU_E_ARG;
+    if (b->orphan) { g_last_error = "sibling batch: its primary has been destroyed"; return FUIFGPU_E_ARG; }
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<std::vector<GroupEntry>> groups;
+    std::vector<int> group_of;
+    OKCHK(stage_streams(b, blobs, sizes, n_images, preview, st, groups, group_of));
+    const char *ord = getenv("FUIFGPU_TILE_ORDER");
+    const WorkList wl = plan_work_list(b->plan, groups, group_of, sizes, b->max_waves, b->waves_per_simd, b->in_flight, ord && !strcmp(ord, "group"));
+    b->cfg = wl.cfg; b->n_waves = wl.n_waves; b->sched = wl.sched; b->n_queues = wl.n_queues; b->n_tiles = (int)wl.tiles.size();
+    OKCHK(reserve_launch_buffers(b, n_images, wl.layout.size()));
+    if (!wl.layout.empty()) HIPCHK(hipMemcpyAsync(b->d_layout, wl.layout.data(), wl.layout.size() * 4, hipMemcpyHostToDevice, st));
+    if (b->n_tiles) HIPCHK(hipMemcpyAsync(b->d_tiles, wl.tiles.data(), sizeof(Tile) * (size_t)b->n_tiles, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));  // wl is a local; b->jobs may be rebuilt by the next upload
     b->n_loaded = n_images;
     if (getenv("FUIFGPU_VERBOSE"))
         fprintf(stderr, "fuifgpu: %d images, %d tiles, %s configuration, %d persistent wavefronts (%d per SIMD), %d queues, context scheduler %s\n", n_images, b->n_tiles,
@@ -578,36 +575,22 @@ int fuifgpu_batch_decode(fuifgpu_batch *b, void *stream) {
     const fuifgpu_batch *r = launch_res(b);
     P.tables = b->d_tables; P.scratch = r->d_scratch; P.scratch_stride = b->scratch_stride; P.bfs_off = b->bfs_off; P.leaves_off = b->leaves_off;
     P.stack_off = b->stack_off; P.queue_off = b->queue_off; P.subtree_off = b->subtree_off; P.max_properties = b->plan.max_properties; P.max_nodes = b->max_nodes; P.max_super = maniac_max_supernodes(b->max_nodes); P.prof = b->d_prof;
-    if (b->want_tile_log && b->tile_log_cap < b->n_tiles) {
-        hipFree(b->d_tile_log); b->d_tile_log = nullptr; b->tile_log_cap = 0;
-        HIPCHK(hipMalloc((void **)&b->d_tile_log, sizeof(unsigned long long) * 4 * (size_t)b->n_tiles));
-        b->tile_log_cap = b->n_tiles;
-    }
+    if (b->want_tile_log) OKCHK(grow(b->d_tile_log, b->tile_log_cap, b->n_tiles, sizeof(unsigned long long) * 4));
     P.tile_log = b->want_tile_log ? b->d_tile_log : nullptr;   // (only -DFUIF_STATS / -DFUIF_PROF / -DFUIF_TILELOG kernels write it)
     if (P.tile_log) HIPCHK(hipMemsetAsync(b->d_tile_log, 0, sizeof(unsigned long long) * 4 * (size_t)b->n_tiles, st));   // the running time accumulates over a tile's run segments
     P.tiles = b->d_tiles; P.n_tiles = b->n_tiles; P.sched = b->sched; P.n_queues = b->n_queues;
-    {
-        uint32_t *w = b->d_sched;
-        P.q_head = w; P.done_total = w + 1; P.sched_stats = reinterpret_cast<unsigned long long *>(w + 2); P.started_total = w + 18; P.heartbeat = w + 19;
-        P.ctx_used = reinterpret_cast<unsigned long long *>(w + 20);   // (byte offset 80: 8-byte aligned)
-        w += 24;
-        P.yield_slack = 4;   // (profiles/r4_scheduler_knobs.txt: 4 -> 7.30 s, 8 -> 7.37 s, 16 -> 7.60 s, 32 -> 7.83 s on the trimmed kernel)
-        if (const char *e = getenv("FUIFGPU_YIELD_SLACK")) P.yield_slack = (uint32_t)std::max(0, atoi(e));
-        P.prio_base = kDefaultPrioBase;   // size classes <= base run at wavefront priority 3, base+1 at 2, base+2 at 1; negative: all 0
-        if (const char *e = getenv("FUIFGPU_PRIO_BASE")) P.prio_base = atoi(e);
-        P.simd_claim = w; w += 2 * 4096 + 1;
-        P.cu_alive = w; w += 4096; P.cu_live = w; w += 4096; P.cu_foreign = w; w += 4096;
-        P.simd_long = w; w += 4 * 4096;
-        P.long_per_simd = 3;
-        if (const char *e = getenv("FUIFGPU_LONG_PER_SIMD")) P.long_per_simd = std::max(0, atoi(e));
-        P.img_next = w; w += b->n_loaded;
-        P.img_done = w; w += b->n_loaded;
-        P.q_turn = w; w += b->n_queues;
-        P.tile_rec = reinterpret_cast<TileRec *>(w);
-        P.q_img_begin = b->d_layout; P.q_images = b->d_layout + b->n_queues + 1; P.img_tile_begin = b->d_layout + b->n_queues + 1 + b->n_loaded;
-        P.ctx_scratch = r->d_ctx;
-        P.ctx_units_per_queue = b->share ? (uint32_t)std::min<size_t>(r->ctx_bytes / (size_t)std::max(b->n_queues, 1) / 256, (size_t)0xFFFFFF00u / (size_t)std::max(b->n_queues, 1)) : b->ctx_units_per_queue;
-    } P.progress = b->d_progress; P.group_start = b->d_group_start;
+    sched_layout(b->n_loaded, b->n_queues, b->sched ? b->n_tiles : 0, b->d_sched, &P);
+    P.yield_slack = 4;   // (profiles/r4_scheduler_knobs.txt: 4 -> 7.30 s, 8 -> 7.37 s, 16 -> 7.60 s, 32 -> 7.83 s on the trimmed kernel)
+    if (const char *e = getenv("FUIFGPU_YIELD_SLACK")) P.yield_slack = (uint32_t)std::max(0, atoi(e));
+    P.prio_base = kDefaultPrioBase;   // size classes <= base run at wavefront priority 3, base+1 at 2, base+2 at 1; negative: all 0
+    if (const char *e = getenv("FUIFGPU_PRIO_BASE")) P.prio_base = atoi(e);
+    P.long_per_simd = 3;
+    if (const char *e = getenv("FUIFGPU_LONG_PER_SIMD")) P.long_per_simd = std::max(0, atoi(e));
+    const QueueLayout L = queue_layout(b->n_queues, b->n_loaded);
+    P.q_img_begin = b->d_layout + L.q_img_begin; P.q_images = b->d_layout + L.q_images; P.img_tile_begin = b->d_layout + L.img_tile_begin;
+    P.ctx_scratch = r->d_ctx;
+    P.ctx_units_per_queue = b->share ? ctx_units_per_queue(r->ctx_bytes, b->n_queues) : b->ctx_units_per_queue;   // (a sibling decodes out of the primary's frozen arena)
+    P.progress = b->d_progress; P.group_start = b->d_group_start;
     HIPCHK(hipEventRecord(b->ev[0], st));
     launch_maniac_decode(P, b->n_waves, b->cfg, b->n_tiles > b->n_loaded ? 1 : 0, st);
     HIPCHK(hipGetLastError());
@@ -874,11 +857,10 @@ int fuifgpu_batch_sched_stats(fuifgpu_batch *b, uint64_t *out8) {
     return FUIFGPU_E_UNSUPPORTED;
 #endif
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out8, b->d_sched + 2, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out8, (const uint8_t *)b->d_sched + offsetof(SchedHeader, sched_stats), sizeof(SchedHeader::sched_stats), hipMemcpyDeviceToHost));
     return FUIFGPU_OK;
 }
 
-// ---- device memory for callers that are not HIP programs themselves (the C++ boundary layer is compiled with g++) ---
 // ---- device selection (one node, several GPUs: images are independent units) ---------------------------------------
 int fuifgpu_device_count(int *n_devices) {
     if (!n_devices) return FUIFGPU_E_ARG;
@@ -932,6 +914,7 @@ int fuifgpu_peer_copy(void *dst_device_ptr, int dst_device, const void *src_devi
     return FUIFGPU_OK;
 }
 
+// ---- device memory for callers that are not HIP programs themselves (the C++ boundary layer is compiled with g++) ---
 void *fuifgpu_dev_alloc(size_t bytes) {
     void *p = nullptr;
     if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { g_last_error = "hipMalloc failed (no HIP device or out of memory): libfuifgpu has no CPU fallback"; return nullptr; }

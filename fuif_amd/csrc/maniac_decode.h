@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "fuifgpu_internal.h"
 
 namespace fuifgpu {
@@ -66,10 +68,10 @@ struct DecodeParams {
     uint32_t *done_total;        // sched 1: tiles finished; zeroed before the launch
     uint32_t *started_total;     // sched 1: tiles started; once it reaches n_tiles a wavefront without work can only ever resume tiles of its own CU
     uint32_t *heartbeat;         // bumped every few rows by every running tile: "no progress anywhere" is what a stall verdict needs, not "I was idle long"
-    uint32_t *cu_alive;          // sched 1: [4096] per CU key: wavefronts that have arrived and not retired
-    uint32_t *cu_live;           // sched 1: [4096] per CU key: tiles started on that CU and not finished (running or suspended)
-    uint32_t *cu_foreign;        // sched 1: [4096] per CU key: those of them that belong to another queue than the CU's home queue
-    uint32_t *simd_long;         // sched 1: [4096 * 4] per CU key and SIMD: long tiles (>= 1/8 of their picture) running on that SIMD right now
+    uint32_t *cu_alive;          // sched 1: [kCuKeys] per CU key: wavefronts that have arrived and not retired
+    uint32_t *cu_live;           // sched 1: [kCuKeys] per CU key: tiles started on that CU and not finished (running or suspended)
+    uint32_t *cu_foreign;        // sched 1: [kCuKeys] per CU key: those of them that belong to another queue than the CU's home queue
+    uint32_t *simd_long;         // sched 1: [kCuKeys * kSimdsPerCu] per CU key and SIMD: long tiles (>= 1/8 of their picture) running on that SIMD right now
     int32_t long_per_simd;       // a wavefront does not start / resume a long tile while its SIMD runs this many already, unless it has been idle for a
                                  // while (0: no such rule).  Long tiles are the launch's critical path; by chance a SIMD got 1 to 7 of them and each extra
                                  // one costs the others ~1 % (profiles/r3_stragglers.txt)
@@ -79,7 +81,7 @@ struct DecodeParams {
     unsigned long long *ctx_used; // sched 1: units handed out from the bottom (low word: long tiles) and from the top (high word: the others) of the arena -- bump
                                  //          allocation, a launch never frees; zeroed before the launch
     unsigned long long *sched_stats; // -DFUIF_STATS builds, sched 1: {ticks wavefronts spent without work before the last tile finished, tiles picked up, suspensions, ...}; zeroed before the launch
-    uint32_t *simd_claim;        // [2 * 4096 + 1] {arrivals, 1 + dense index} per physical CU key, then the CU counter; zeroed before the launch
+    uint32_t *simd_claim;        // [2 * kCuKeys + 1] {arrivals, 1 + dense index} per physical CU key, then the CU counter at [2 * kCuKeys]; zeroed before the launch
     uint32_t *progress;          // [n_images][n_channels] 0 = nothing yet, 1 + rows finished once the header is known; zeroed before the launch
     uint32_t *group_start;       // [n_images][n_channels] 1 + byte offset of the group that starts at this channel (0 = none); zeroed before the launch
     uint8_t *scratch;            // per wavefront: parse-order nodes | breadth-first nodes | leaves | parse stack | BFS queue
@@ -90,6 +92,39 @@ struct DecodeParams {
     unsigned long long *prof;    // -DFUIF_PROF builds: 8 cycle counters per stream (else unused)
     unsigned long long *tile_log; // -DFUIF_STATS builds: [n_tiles][4] {image << 32 | first channel, start, end, waited} in s_memrealtime ticks (100 MHz); waited's top 16 bits = SIMD key
 };
+
+// Scheduler state of a launch: ONE buffer of 32-bit words, zeroed before every launch -- a SchedHeader, then the arrays in the
+// order sched_layout() walks them.  This is the only place that knows the order.
+constexpr uint32_t kCuKeys = 4096;        // physical CU keys: cu / sh / se (8 bits) | XCC (4 bits)
+constexpr uint32_t kSimdsPerCu = 4;
+constexpr uint32_t kSchedStatWords = 8;   // 64-bit statistics words (fuifgpu_batch_sched_stats)
+struct SchedHeader {
+    uint32_t q_head, done_total;
+    unsigned long long sched_stats[kSchedStatWords];
+    uint32_t started_total, heartbeat;
+    unsigned long long ctx_used, pad;
+};
+static_assert(sizeof(SchedHeader) == 96, "the scheduler header is 24 words");
+static_assert(offsetof(SchedHeader, sched_stats) % 8 == 0 && offsetof(SchedHeader, ctx_used) % 8 == 0, "64-bit atomics");
+// Words of the whole buffer for a launch of n_images over n_queues with n_tile_recs tile records (sched == 1: one per tile).
+// With `base` and P: P's scheduler pointers are set to their places in the buffer at `base`.
+inline size_t sched_layout(int n_images, int n_queues, int n_tile_recs, uint32_t *base = nullptr, DecodeParams *P = nullptr) {
+    DecodeParams count_only;
+    if (!P) { P = &count_only; base = nullptr; }
+    size_t w = sizeof(SchedHeader) / 4;
+    auto take = [&](size_t n) { uint32_t *p = base ? base + w : nullptr; w += n; return p; };
+    P->simd_claim = take(2 * kCuKeys + 1); P->cu_alive = take(kCuKeys); P->cu_live = take(kCuKeys); P->cu_foreign = take(kCuKeys);
+    P->simd_long = take(kSimdsPerCu * kCuKeys); P->img_next = take(n_images); P->img_done = take(n_images); P->q_turn = take(n_queues);
+    P->tile_rec = reinterpret_cast<TileRec *>(take((size_t)n_tile_recs * (sizeof(TileRec) / 4)));
+    if (SchedHeader *h = reinterpret_cast<SchedHeader *>(base)) {
+        P->q_head = &h->q_head; P->done_total = &h->done_total; P->sched_stats = h->sched_stats;
+        P->started_total = &h->started_total; P->heartbeat = &h->heartbeat; P->ctx_used = &h->ctx_used;
+    }
+    return w;
+}
+// The queue / image table of sched == 1, one buffer of words too: q_img_begin [n_queues + 1] | q_images [n_images] | img_tile_begin [n_images + 1]
+struct QueueLayout { size_t q_img_begin, q_images, img_tile_begin, words; };   // word offsets of the three, words in all
+inline QueueLayout queue_layout(size_t n_queues, size_t n_images) { return {0, n_queues + 1, n_queues + 1 + n_images, n_queues + 1 + 2 * n_images + 1}; }
 
 int maniac_max_supernodes(int max_nodes);
 size_t maniac_scratch_bytes(int max_nodes, size_t *bfs_off, size_t *leaves_off, size_t *stack_off, size_t *queue_off, size_t *subtree_off);

@@ -908,7 +908,7 @@ __global__ __launch_bounds__(64) FUIF_OCCUPANCY void k_maniac_decode(DecodeParam
         if (lane == 0) {
             atomicAdd(&P.cu_alive[key], 1u);
             if (atomicAdd(&P.simd_claim[2 * key], 1u) == 0u) {
-                idx = atomicAdd(&P.simd_claim[2 * 4096], 1u);
+                idx = atomicAdd(&P.simd_claim[2 * kCuKeys], 1u);
                 st_agent(&P.simd_claim[2 * key + 1], idx + 1u);
             } else {
                 uint32_t v = 0;

@@ -42,6 +42,7 @@ def build_emulated_library(extra=(), name="libfuifgpu_emu.so"):
 SELECTED = [
     ("tests/test_gpu_synthetic.py::test_deep_trees_walk_through_chained_supernodes[False]", 50),
     ("tests/test_gpu_group_parallel.py::test_mixed_batch_with_more_tiles_than_wavefronts", 48),
+    ("tests/test_gpu_group_parallel.py::test_one_batch_reused_across_upload_sizes", 48),
     ("tests/test_gpu_synthetic.py::test_deep_trees_walk_through_chained_supernodes[True]", 45),
     ("tests/test_gpu_group_parallel.py::test_previews_of_indexed_streams", 38),
     ("tests/test_zz_gpu_encoder.py", 35),
@@ -99,6 +100,7 @@ def run_dealt(weighted, env, workers, timeout=1700):
 CONCURRENT = [
     "tests/test_gpu_group_parallel.py::test_reference_written_files_indexed_after_the_fact",
     "tests/test_gpu_group_parallel.py::test_mixed_batch_with_more_tiles_than_wavefronts",
+    "tests/test_gpu_group_parallel.py::test_one_batch_reused_across_upload_sizes",
     "tests/test_gpu_group_parallel.py::test_jpeg_like_indexed",
     # round 6: suspended and resumed tiles whose supernodes are narrow / whose leaves are compact (the format flags travel in the tile record)
     "tests/test_gpu_synthetic.py::test_context_formats_of_round_6[True-narrow_compact]",

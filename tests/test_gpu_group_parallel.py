@@ -149,6 +149,38 @@ def test_mixed_batch_with_more_tiles_than_wavefronts(gpulib, port):
     assert len(ngroups) == 1 and ngroups.pop() > 20      # plain streams report their groups too
 
 
+def test_one_batch_reused_across_upload_sizes(gpulib):
+    """ONE batch, three uploads of different sizes -- 2 images, all of them, 3 -- each decoded and undone: the launch buffers grow, the
+    launch goes from the single list to the context scheduler (more tiles than the dense configuration holds wavefronts) and back,
+    and the small launches see scheduler words the large one left behind.  Every round gives the source pictures; the last one
+    equals the same three streams on a fresh batch"""
+    imgs = [photographic(160, 120, 3, 8, seed=500 + k) for k in range(6)]
+    indexed = [gpulib.encode_image(im, 8, tree_mode=1, index=True) for im in imgs]
+    plain = [gpulib.encode_image(im, 8, tree_mode=1) for im in imgs]
+    n = int(os.environ.get("FUIF_TEST_BATCH", "192"))
+    blobs = [(indexed if (k % 3) else plain)[k % 6] for k in range(n)]
+    batch = gpulib.Batch(gpulib.Plan(blobs[0]), n, sum(len(b) for b in blobs))
+    try:
+        for count in (2, n, 3):
+            batch.upload(blobs[:count])
+            batch.decode()
+            batch.sync()
+            st, used = batch.status()
+            pre = [batch.coef_planes(i) for i in range(count)]
+            meta = [batch.channel_meta(i) for i in range(count)]
+            batch.undo_transforms()
+            batch.sync()
+            post = [batch.out_planes(i) for i in range(count)]
+            assert [int(x) for x in st[:count]] == [0] * count, count
+            for k in range(count):
+                assert all(np.array_equal(post[k][i], imgs[k % 6][i]) for i in range(3)), (count, k)
+        reused = dict(pre=pre, meta=meta, post=post, st=[int(x) for x in st[:3]])
+    finally:
+        batch.close()
+    fresh = _run(gpulib, blobs[:3])
+    assert all(_same(reused, fresh, k, k) for k in range(3))
+
+
 def test_jpeg_like_indexed(gpulib, port):
     from fuif_amd.jpeglike import encode_jpeg_like
     img = photographic(136, 120, 3, 8, seed=77, sigma=1.0)
