@@ -854,7 +854,8 @@ struct Builder {
             need.push_back({r.off, (int64_t)r.w * r.h});
         };
         auto clean_coded = [&](const PlaneRef &r) { return r.buf == BUF_COEF && !is_dirty(r); };
-        static const bool enabled = [] { const char *e = getenv("FUIFGPU_INT16_RESIDUALS"); return !e || atoi(e) != 0; }();   // 0: widen everything (A/B, tests)
+        const char *e16 = getenv("FUIFGPU_INT16_RESIDUALS");   // read per plan like the fusion switches: tests run both forms inside one process
+        const bool enabled = !e16 || atoi(e16) != 0;           // 0: widen everything (A/B, tests)
         std::vector<int64_t> made;   // coded planes whose int32 copy a dequantisation WRITES from the int16 samples (nothing to widen for them)
         auto is_made = [&](const PlaneRef &r) { for (int64_t o : made) if (o == r.off) return true; return false; };
         auto want_unless_made = [&](const PlaneRef &r) { if (!(r.buf == BUF_COEF && is_made(r))) want(r); };

@@ -1,5 +1,6 @@
 // fuif_amd/csrc/squeeze_arith.h -- the two integer formulas of the Squeeze transform (transform/squeeze.h:61-77,103-107) in the
-// branch-free form the unsqueeze kernels of transforms.hip run.  A header of its own so that tests/test_squeeze_arith.py can
+// branch-free form the unsqueeze kernels of transforms.hip run, and the per-pair step made of them (unsqueeze_step: what every
+// unsqueeze kernel calls) with the reference's int16 stores.  A header of its own so that tests/test_squeeze_arith.py can
 // compile the very same text for the host and compare it, case by case, with the reference's form.
 #pragma once
 #include <cstdint>
@@ -43,6 +44,22 @@ SQ_DEV int smooth_tendency(int B, int a, int n) {
 SQ_DEV void unsqueeze_pair(int avg, int diff, int &A, int &B) {
     A = avg + ((diff + (int)((unsigned)diff >> 31)) >> 1);
     B = A - diff;
+}
+
+// What an assignment to the reference's pixel_type = int16_t (image/image.h:35) keeps of an int: the low 16 bits, sign-extended
+// (the sums are computed in promoted int; the narrowing conversion is modular).  One v_bfe_i32 on the GPU.
+SQ_DEV int narrow16(int v) { return (int)(int16_t)v; }
+
+// The whole per-pair step of inv_hsqueeze / inv_vsqueeze (squeeze.h:98-108 / :199-214) with the reference's types: `tendency`,
+// `diff`, `A` and `B` are pixel_type there, so each of them is narrowed where the reference assigns it.  left (the previous B;
+// the pair's own avg for the first pair, :91 / :187), avg and next_avg are stored samples, i.e. already int16 values; res is the
+// residual sample.  For such inputs smooth_tendency's own results fit 16 bits (|quotient| <= 8 * 32768 / 12, and a clamp only
+// lowers it), which tests/test_squeeze_arith.py checks against the reference's int16-typed form instead of taking it on trust.
+// What is stored -- and what the next pair sees as `left` -- is the narrowed B.
+SQ_DEV void unsqueeze_step(int left, int avg, int next_avg, int res, int &A, int &B) {
+    const int diff = narrow16(res + smooth_tendency(left, avg, next_avg));   // squeeze.h:102-103: pixel_type diff = diff_minus_tendency + tendency
+    A = narrow16(avg + ((diff + (int)((unsigned)diff >> 31)) >> 1));   // squeeze.h:105: pixel_type A = (...) >> 1, as in unsqueeze_pair
+    B = narrow16(A - diff);                                             // squeeze.h:107: pixel_type B = A - diff, from the narrowed A
 }
 
 }  // namespace fuifgpu

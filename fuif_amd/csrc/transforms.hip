@@ -9,6 +9,12 @@
 //   k_inv_ycocg      transform/ycocg.h:49-61       elementwise on three planes (+ clamp)
 //   k_inv_ycbcr      transform/ycbcr.h:49-60       float operands, double arithmetic, no FMA
 //   k_dequant        transform/quantize.h:32-49    elementwise * Channel::q (per image, per plane)
+//
+// The reference's samples are pixel_type = int16_t (image/image.h:35).  The planes here are int32 containers of such values: the unsqueeze
+// kernels (squeeze_arith.h: unsqueeze_step), k_dequant and the dequantising load of k_idct8x8 store what an assignment to pixel_type keeps
+// (narrow16); the other kernels' results fit 16 bits for int16 inputs (clamps, copies, averages) or are outside the reference's defined
+// behaviour when they do not (the iDCT's round() into pixel_type, dct.h:289).  k_inv_approx and the soft-match kernels narrow their sums likewise
+// (approximate.h:53-55, 2dmatch.h:129,155).
 //   k_idct8x8        transform/dct.h:88-107,282-291 FP64, reference summation order, no FMA
 //   k_upsample       transform/subsample.h:90-115  "fancy" 2x chroma upsampling
 //   k_clamp / k_copy_clamp   image/image.cpp:107-113
@@ -75,9 +81,8 @@ __global__ __launch_bounds__(256) void k_inv_vsqueeze(Bases b, PlaneRef pa, Plan
         }
 #pragma unroll
         for (int k = 0; k < VS_STEP; k++) {
-            const int diff = rv[k] + smooth_tendency(prevB, avg, nv[k]);
             int A, B;
-            unsqueeze_pair(avg, diff, A, B);
+            unsqueeze_step(prevB, avg, nv[k], rv[k], A, B);
             o[(int64_t)(2 * (y + k)) * w] = clamp ? clampi(A, lo, hi) : A;
             o[(int64_t)(2 * (y + k) + 1) * w] = clamp ? clampi(B, lo, hi) : B;
             prevB = B;
@@ -87,9 +92,8 @@ __global__ __launch_bounds__(256) void k_inv_vsqueeze(Bases b, PlaneRef pa, Plan
     for (; y < h2; y++) {
         const int next_avg = (y + 1 < h1) ? a[(int64_t)(y + 1) * w] : avg;
         const int res = r[(int64_t)y * w];
-        const int diff = res + smooth_tendency(prevB, avg, next_avg);
         int A, B;
-        unsqueeze_pair(avg, diff, A, B);
+        unsqueeze_step(prevB, avg, next_avg, res, A, B);
         o[(int64_t)(2 * y) * w] = clamp ? clampi(A, lo, hi) : A;
         o[(int64_t)(2 * y + 1) * w] = clamp ? clampi(B, lo, hi) : B;
         prevB = B;
@@ -144,9 +148,8 @@ __global__ __launch_bounds__(256) void k_inv_hsqueeze_rows(Bases b, PlaneRef pa,
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const int next_avg = nv[q].v[k];
-                const int diff = rv[q].v[k] + smooth_tendency(left, avg, next_avg);
                 int A, B;
-                unsqueeze_pair(avg, diff, A, B);
+                unsqueeze_step(left, avg, next_avg, rv[q].v[k], A, B);
                 left = B;
                 avg = next_avg;
                 if (clamp) { A = clampi(A, lo, hi); B = clampi(B, lo, hi); }
@@ -158,9 +161,8 @@ __global__ __launch_bounds__(256) void k_inv_hsqueeze_rows(Bases b, PlaneRef pa,
     }
     for (; x < w2; x++) {
         const int next_avg = x + 1 < w1 ? a[x + 1] : avg;   // squeeze.h:100
-        const int diff = r[x] + smooth_tendency(left, avg, next_avg);
         int A, B;
-        unsqueeze_pair(avg, diff, A, B);
+        unsqueeze_step(left, avg, next_avg, r[x], A, B);
         o[2 * x] = clamp ? clampi(A, lo, hi) : A;
         o[2 * x + 1] = clamp ? clampi(B, lo, hi) : B;
         left = B;
@@ -239,9 +241,8 @@ __global__ __launch_bounds__(64) void k_inv_hsqueeze_tiles(Bases b, PlaneRef pa,
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const int next_avg = nn[k];
-                const int diff = rr[k] + smooth_tendency(left, avg, next_avg);
                 int A2, B2;
-                unsqueeze_pair(avg, diff, A2, B2);
+                unsqueeze_step(left, avg, next_avg, rr[k], A2, B2);
                 left = B2;
                 avg = next_avg;
                 if (clamp) { A2 = clampi(A2, lo, hi); B2 = clampi(B2, lo, hi); }
@@ -268,9 +269,8 @@ __global__ __launch_bounds__(64) void k_inv_hsqueeze_tiles(Bases b, PlaneRef pa,
     if (!mine) return;
     for (; x < w2; x++) {
         const int next_avg = x + 1 < w1 ? a[x + 1] : avg;   // squeeze.h:100
-        const int diff = r[x] + smooth_tendency(left, avg, next_avg);
         int A2, B2;
-        unsqueeze_pair(avg, diff, A2, B2);
+        unsqueeze_step(left, avg, next_avg, r[x], A2, B2);
         o[2 * x] = clamp ? clampi(A2, lo, hi) : A2;
         o[2 * x + 1] = clamp ? clampi(B2, lo, hi) : B2;
         left = B2;
@@ -357,9 +357,8 @@ __global__ __launch_bounds__(64) void k_inv_hsq2_ycocg(Bases b, PlaneRef pa0, Pl
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const int next_avg = nn[k];
-                    const int diff = rr[k] + smooth_tendency(left[c], avg[c], next_avg);
                     int A2, B2;
-                    unsqueeze_pair(avg[c], diff, A2, B2);
+                    unsqueeze_step(left[c], avg[c], next_avg, rr[k], A2, B2);
                     left[c] = B2;
                     avg[c] = next_avg;
                     ov[2 * k] = A2; ov[2 * k + 1] = B2;
@@ -403,8 +402,7 @@ __global__ __launch_bounds__(64) void k_inv_hsq2_ycocg(Bases b, PlaneRef pa0, Pl
             const int32_t *a = c ? a1 : a0;
             const TR *r = c ? r1 : r0;
             const int next_avg = x + 1 < w1 ? a[x + 1] : avg[c];   // squeeze.h:100
-            const int diff = r[x] + smooth_tendency(left[c], avg[c], next_avg);
-            unsqueeze_pair(avg[c], diff, P[c][0], P[c][1]);
+            unsqueeze_step(left[c], avg[c], next_avg, r[x], P[c][0], P[c][1]);
             left[c] = P[c][1];
             avg[c] = next_avg;
         }
@@ -468,6 +466,7 @@ __global__ __launch_bounds__(256) void k_inv_ycbcr(Bases b, PlaneRef p0, PlaneRe
 // grid.y walks the op's plane list.
 // TR = coef_t (Op::r16): the planes are coded planes nobody has touched -- read the int16 samples from the coefficient slab and write
 // sample * q into the int32 copy (widening and scaling in one pass, also when q == 1); TR = int32_t: in place on the int32 copy.
+// quantize.h:41 is `ch.value(y,x) *= q` on a pixel_type &: the product is computed in int and stored as int16 (narrow16), in both forms.
 template <typename TR>
 __global__ __launch_bounds__(256) void k_dequant(Bases b, const PlaneRef *list, const ChannelMeta *meta, int n_channels, int img_first) {
     const PlaneRef p = list[blockIdx.y];
@@ -477,7 +476,7 @@ __global__ __launch_bounds__(256) void k_dequant(Bases b, const PlaneRef *list, 
     const int64_t n = (int64_t)p.w * p.h;
     int32_t *d = plane_ptr(b, p, blockIdx.z);
     const TR *s = residual_ptr<TR>(b, p, blockIdx.z);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) d[i] = (int)s[i] * q;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) d[i] = narrow16((int)s[i] * q);
 }
 
 __global__ __launch_bounds__(256) void k_clamp(Bases b, PlaneRef src, PlaneRef dst, int lo, int hi) {
@@ -536,7 +535,7 @@ __global__ __launch_bounds__(256) void k_inv_approx(Bases b, PlaneRef pc, PlaneR
     int32_t *d = plane_ptr(b, pc, blockIdx.z);
     const int32_t *r = plane_ptr(b, pr, blockIdx.z);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        d[i] = d[i] * q + (have ? r[i] : 0);
+        d[i] = narrow16(narrow16(d[i] * q) + (have ? r[i] : 0));   // approximate.h:53,55: `*= q`, then `+=`, each on a pixel_type &
     if (have && m && blockIdx.x == 0 && threadIdx.x == 0 && pc.qsrc >= 0 && pr.qsrc >= 0) m[pc.qsrc].q = reached ? m[pr.qsrc].q : 1;
 }
 
@@ -566,7 +565,7 @@ __global__ __launch_bounds__(256) void k_inv_match_frames(Bases b, PlaneRef pm, 
         for (int k = 0; k < n_list; k++) {
             int32_t *p = plane_ptr(b, list[k], z_img);
             const int sv = inside ? p[src] : 0;
-            p[(int64_t)y * w + x] = softmatch ? p[(int64_t)y * w + x] + sv : sv;
+            p[(int64_t)y * w + x] = softmatch ? narrow16(p[(int64_t)y * w + x] + sv) : sv;   // 2dmatch.h:155: `+=` on a pixel_type &
         }
     }
 }
@@ -580,7 +579,7 @@ __global__ __launch_bounds__(256) void k_inv_match_frames(Bases b, PlaneRef pm, 
 // Soft matches (value += source, :136-140; the CLI never writes them, fuif.cpp:445) take the same route with one accumulator
 // per listed plane: value(p) = residual(p) + value(source(p)), so A[p] = residual(p) for a matched sample and 0 for a root,
 // every doubling step adds A[S[p]] to A[p] (two copies of the accumulators, read one / write the other), and the gather adds
-// the root's sample.  Forward references (only possible in images narrower than the spiral) are flagged
+// the root's sample and keeps the low 16 bits, sign-extended: the reference's `+=` stores a pixel_type at every link.  Forward references (only possible in images narrower than the spiral) are flagged
 // FUIFGPU_ST_UNSUPPORTED and the image is left unmatched.
 // The list of a soft match is [planes (n), accumulators (n), accumulators (n)]; Op::p1 of a jump / apply op = which copy it reads.
 DEV void match_offset(int code, int &xo, int &yo) {   // 2dmatch.h:50-78
@@ -641,7 +640,8 @@ __global__ __launch_bounds__(256) void k_match_jump(Bases b, PlaneRef pm, PlaneR
         if (softmatch)
             for (int k = 0; k < n_list; k++) {
                 const int32_t *a = plane_ptr(b, list[n_list * (1 + from) + k], blockIdx.z);
-                plane_ptr(b, list[n_list * (2 - from) + k], blockIdx.z)[p] = a[p] + (s >= 0 ? a[s] : 0);
+                // (unsigned: a long chain's sum may pass 2^31; only its low 16 bits are kept in the end)
+                plane_ptr(b, list[n_list * (2 - from) + k], blockIdx.z)[p] = (int32_t)((uint32_t)a[p] + (uint32_t)(s >= 0 ? a[s] : 0));
             }
     }
 }
@@ -658,7 +658,8 @@ __global__ __launch_bounds__(256) void k_match_apply(Bases b, PlaneRef pm, Plane
         for (int k = 0; k < n_list; k++) {
             int32_t *pl = plane_ptr(b, list[k], blockIdx.z);
             const int root = s < 0 ? 0 : pl[s];
-            pl[p] = softmatch ? plane_ptr(b, list[n_list * (1 + from) + k], blockIdx.z)[p] + root : root;
+            // 2dmatch.h:129: `+=` on a pixel_type & at every link of the chain; narrowing is a ring homomorphism, so narrowing the whole sum once gives the same value
+            pl[p] = softmatch ? narrow16((int)((uint32_t)plane_ptr(b, list[n_list * (1 + from) + k], blockIdx.z)[p] + (uint32_t)root)) : root;
         }
     }
 }
@@ -726,7 +727,8 @@ DEV void idct_1d(const double (&in)[8], double (&out)[8]) {
     }
 }
 // A source plane of kind BUF_COEF16Q (planner peephole fuse_dequant_into_idct) is a coded plane as the entropy kernel stored it: the int16 sample is
-// read from the coefficient slab and multiplied by the channel's quantisation constant on the way in (quantize.h:32-49 folded into the load).
+// read from the coefficient slab and multiplied by the channel's quantisation constant on the way in (quantize.h:32-49 folded into the load;
+// the product narrowed to int16 like the store of quantize.h:41 that it replaces).
 // kAc16 (Op::pad2): ALL 63 AC planes are of that kind -- known at compile time, so the 8 loads of a column are issued together as before; only the DC plane
 // (entry 0: a product of the unsqueeze chain in a default stream) is tested at run time.  With a per-plane test inside the loop every load waited for
 // its own round trip and the kernel's time doubled (23 -> 45 ms per C3 step, profiles/r5_c3_kernel_stats_scalar_q_loads.csv).
@@ -754,7 +756,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
             const PlaneRef p = list[u * 8 + x];
             int v;
             if ((u != 0 || x != 0) ? kAc16 : p.buf == BUF_COEF16Q)
-                v = (int)(b.c16 + (int64_t)blockIdx.z * b.stride[BUF_COEF] + p.off)[(int64_t)by * p.w + bx] * qs[u * 8 + x];
+                v = narrow16((int)(b.c16 + (int64_t)blockIdx.z * b.stride[BUF_COEF] + p.off)[(int64_t)by * p.w + bx] * qs[u * 8 + x]);
             else
                 v = plane_ptr(b, p, blockIdx.z)[(int64_t)by * p.w + bx];
             col[u] = (u == 0 && x == 0) ? (double)__fadd_rn((float)v, dcoff) : (double)v;
@@ -968,7 +970,7 @@ __global__ __launch_bounds__(256) void k_fwd_vsqueeze(const int32_t *in, int w, 
     res[(int64_t)y * w + x] = (A - B) - smooth_tendency(top, a, next);
 }
 __global__ __launch_bounds__(256) void k_scale(int32_t *d, int64_t n, int q) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) d[i] *= q;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) d[i] = narrow16(d[i] * q);   // quantize.h:41
 }
 void launch_scale(int32_t *plane, int64_t n, int q, hipStream_t stream) {
     if (n <= 0 || q == 1) return;

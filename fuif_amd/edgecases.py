@@ -1,0 +1,232 @@
+"""Seeded hand-made FUIF streams at the edges of the reference's 16-bit sample type.
+
+The reference keeps every sample in pixel_type = int16_t (image/image.h:35) and narrows whatever its inverse transforms compute when they
+store it (squeeze.h:92-107,189-213; quantize.h:41,44-45; approximate.h:53-55; 2dmatch.h:129,155).  Streams a real encoder writes from pictures of at most 14 bits never reach
+that edge, so the streams here are written directly in the transform domain: raw channels with explicit transform words through the
+product's writer (fuifgpu_encode_channels, squeeze = 0 in the options unless a case says otherwise), the way fuif_amd/jpeglike.py
+does.  The writer takes each channel's range from its data, so the ranges below are the coded ranges; every coded channel stays inside
+what check_bit_depth (encoding.cpp:61-72) accepts: 15 bits of magnitude, maxval - minval <= 32767 where the predictor is not 0 (the
+writer gives the first nb_channels channels predictor 2 and every other channel -- the residuals, the AC coefficients -- predictor 0).
+Every stream is valid: the reference decodes it with `ok`, and its arithmetic on it is defined (int sums, modular narrowing).
+
+CASES is the list the CPU test (oracle == real reference) and the GPU test (kernels == oracle == real reference) share; a case is a
+pure function of its entry.  `wraps` says whether the case is meant to leave 16 bits.  The number beside each wrapping case is the
+count of post-transform samples on which a decoder that keeps the inverse chain in int32 (this repository before the int16 stores were
+matched) differed from the real reference, measured once on the CPU; each is at least 0.5 % of the case's samples.
+"""
+import ctypes as C
+
+import numpy as np
+
+from .jpeglike import DCT_CSHIFTS, ZIGZAG, _dct_matrix
+
+TR_YCOCG, TR_DCT, TR_QUANTIZE, TR_SQUEEZE, TR_2DMATCH, TR_APPROXIMATE = 1, 4, 5, 7, 8, 10   # transform ids of the format (transform/transform.h)
+
+
+class _RawChannel(C.Structure):
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("hshift", C.c_int32), ("vshift", C.c_int32), ("hcshift", C.c_int32),
+                ("vcshift", C.c_int32), ("component", C.c_int32), ("q", C.c_int32), ("data", C.c_void_p)]
+
+
+def encode_channels(chans, w, h, nb_channels, bit_depth, words, squeeze=0):
+    """chans: [dict(w, h, hshift, vshift, hcshift, vcshift, component, q, data=int array h x w)] -> .fuif bytes"""
+    import fuif_amd
+    L = fuif_amd.lib()
+    keep = [np.ascontiguousarray(c["data"], dtype=np.int32).reshape(c["h"], c["w"]) for c in chans]
+    for c, d in zip(chans, keep):
+        if d.size:
+            lo, hi = int(d.min()), int(d.max())
+            assert max(abs(lo), abs(hi)) <= 32767, "coded channel outside 15 bits of magnitude"
+            assert c.get("predictor0", False) or hi - lo <= 32767, "range of a predicted channel beyond check_bit_depth"
+    arr = (_RawChannel * len(chans))(*[_RawChannel(c["w"], c["h"], c["hshift"], c["vshift"], c["hcshift"], c["vcshift"], c["component"], c.get("q", 1),
+                                                   d.ctypes.data) for c, d in zip(chans, keep)])
+    tw = np.array(words, np.int32)
+    opt = fuif_amd.make_encode_options(0, int(squeeze), 12, 1, 4095, 0, int(fuif_amd.DEFAULT_SPLIT_BITS), 0, 0)
+    out, n = C.c_void_p(), C.c_size_t(0)
+    L.fuifgpu_encode_channels.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                          C.POINTER(fuif_amd.EncodeOptions), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    fuif_amd._check(L.fuifgpu_encode_channels(arr, len(chans), w, h, nb_channels, bit_depth, tw.ctypes.data, len(words), C.byref(opt), C.byref(out), C.byref(n)))
+    blob = C.string_at(out.value, n.value)
+    L.fuifgpu_free_blob(out)
+    return blob
+
+
+def _picture_channels(w, h, n):
+    return [dict(w=w, h=h, hshift=0, vshift=0, hcshift=0, vcshift=0, component=c, q=1) for c in range(n)]
+
+
+def squeeze_layout(chans, params, nb_channels):
+    """the channel list after the Squeeze steps `params` (triples type, beginc, endc): geometry and shifts as the decoder derives
+    them (squeeze.h:323-360); `base` marks a channel that is an average (not inserted as a residual by one of the steps)"""
+    chans = [dict(c, base=True) for c in chans]
+    for i in range(0, len(params), 3):
+        horizontal, in_place = params[i] & 1, not (params[i] & 2)
+        beginc, endc = params[i + 1], params[i + 2]
+        offset = endc + 1 if in_place else nb_channels
+        for c in range(beginc, endc + 1):
+            a = chans[c]
+            d = dict(hcshift=a["hcshift"], vcshift=a["vcshift"], component=a["component"], q=1, base=False)
+            if horizontal:
+                w = a["w"]
+                a["w"] = (w + 1) // 2; a["hshift"] += 1; a["hcshift"] += 1
+                d["w"], d["h"] = w - (w + 1) // 2, a["h"]
+            else:
+                h = a["h"]
+                a["h"] = (h + 1) // 2; a["vshift"] += 1; a["vcshift"] += 1
+                d["h"], d["w"] = h - (h + 1) // 2, a["w"]
+            d["hshift"], d["vshift"] = a["hshift"], a["vshift"]
+            chans.insert(offset + c - beginc, d)
+    return chans
+
+
+def _fill(rng, ch, lo, hi):
+    """uniform over lo..hi, then every other sample (at random) redrawn from the outer eighths of the range: sums leave 16 bits where
+    large averages meet large residuals, and uniform samples alone rarely do in a 14-bit case"""
+    shape = (ch["h"], ch["w"])
+    d = rng.integers(lo, hi + 1, shape, dtype=np.int32)
+    eighth = max(1, (hi - lo) // 8)
+    outer = np.where(rng.integers(0, 2, shape) == 1, hi - rng.integers(0, eighth + 1, shape), lo + rng.integers(0, eighth + 1, shape)).astype(np.int32)
+    ch["data"] = np.where(rng.integers(0, 2, shape) == 1, outer, d)
+    if ch["data"].size >= 2:                      # both ends of the range are present: the coded range is exactly lo..hi
+        ch["data"].flat[0], ch["data"].flat[-1] = lo, hi
+
+
+def squeeze_only(w, h, avg_max, res_max, seed):
+    """one channel, three Squeeze levels h, v, h with explicit parameters; average 0..avg_max, residuals -res_max..res_max"""
+    rng = np.random.default_rng(seed)
+    params = [1, 0, 0, 0, 0, 0, 1, 0, 0]
+    chans = squeeze_layout(_picture_channels(w, h, 1), params, 1)
+    for c in chans:
+        if c["base"]:
+            _fill(rng, c, 0, avg_max)
+        else:
+            c["predictor0"] = True
+            _fill(rng, c, -res_max, res_max)
+    return encode_channels(chans, w, h, 1, 14, [TR_SQUEEZE, len(params)] + params)
+
+
+def ycocg_squeeze(w, h, seed):
+    """three channels, YCoCg, then the chroma planes squeezed horizontally and vertically the way the default parameters start
+    (squeeze.h:277-280: not in place, residuals behind the picture's channels): the chain whose last two unsqueezes and colour
+    transform the planner fuses into OP_HSQ2_YCOCG.  Chroma averages -16383..16383, chroma residuals -32767..32767."""
+    rng = np.random.default_rng(seed)
+    params = [3, 1, 2, 2, 1, 2]
+    chans = squeeze_layout(_picture_channels(w, h, 3), params, 3)
+    for i, c in enumerate(chans):
+        if i == 0:
+            _fill(rng, c, 0, 16383)
+        elif c["base"]:
+            _fill(rng, c, -16383, 16383)
+        else:
+            c["predictor0"] = True
+            _fill(rng, c, -32767, 32767)
+    return encode_channels(chans, w, h, 3, 14, [TR_YCOCG, 0, TR_SQUEEZE, len(params)] + params)
+
+
+def quantize_only(w, h, q, amp, seed):
+    """one channel of samples -amp..amp with quantisation constant q and the transform list [Quantize]"""
+    rng = np.random.default_rng(seed)
+    c = _picture_channels(w, h, 1)[0]
+    c["q"] = q
+    _fill(rng, c, -amp, amp)
+    return encode_channels([c], w, h, 1, 14, [TR_QUANTIZE, 0])
+
+
+def approximate(w, h, q, amp, rem, seed):
+    """one channel of quotients -amp..amp with the transform list [Approximate(q)] and its remainder channel -rem..rem behind it
+    (approximate.h:62-78): the inverse is quotient * q, stored, then + remainder, stored (:53-55)"""
+    rng = np.random.default_rng(seed)
+    c, r = _picture_channels(w, h, 1)[0], _picture_channels(w, h, 1)[0]
+    _fill(rng, c, -amp, amp)
+    r["predictor0"] = True
+    _fill(rng, r, -rem, rem)
+    return encode_channels([c, r], w, h, 1, 14, [TR_APPROXIMATE, 3, 0, 0, q - 1])
+
+
+def soft_match(w, h, amp, seed, chain=False):
+    """one channel -amp..amp behind a match meta-channel of free offsets 0..4 (0 = unmatched; 1..4 = the left, upper left, upper and
+    upper right neighbour, 2dmatch.h:50-78) with the transform list [2DMatch(soft)]: a matched sample is its coded value + its source's
+    final value, stored (2dmatch.h:129) -- chains of sums that leave 16 bits.  chain: every sample but the first is matched to its
+    left neighbour (in linear order, so across the rows as well) and the coded values are -40..299 -- the planes of
+    tests/test_gpu_transform_exports.py::test_inv_match_free_offsets_export at density 1.0: one chain through the whole plane, a running
+    sum that passes 2^16 several times"""
+    rng = np.random.default_rng(seed)
+    m, c = _picture_channels(w, h, 1)[0], _picture_channels(w, h, 1)[0]
+    m["data"] = rng.integers(0, 5, (h, w), dtype=np.int32)
+    m["data"].flat[0], m["data"].flat[-1] = 0, 4
+    c["predictor0"] = True
+    if chain:
+        m["data"][:] = 1
+        m["data"].flat[0] = 0
+        c["data"] = rng.integers(-40, 300, (h, w), dtype=np.int32)
+    else:
+        _fill(rng, c, -amp, amp)
+    return encode_channels([m, c], w, h, 1, 14, [TR_2DMATCH, 4, 0, 0, 1, 1000000])
+
+
+def idct_outputs(dc, ac, qdc, qac, maxval):
+    """float64 outputs of the reference's inverse DCT (dct.h:281-289) for blocks whose dequantised coefficients are the int16 the
+    reference stores: dc [bh, bw], ac [63, bh, bw] in channel order (zig-zag rank 1..63), q per channel"""
+    K = _dct_matrix()
+    nat_of_pos = np.argsort(ZIGZAG)
+    bh, bw = dc.shape
+    blocks = np.zeros((bh, bw, 64), np.float64)
+    blocks[:, :, 0] = (dc.astype(np.int64) * qdc).astype(np.int16).astype(np.float64) + np.float32((maxval + 1.0) * 4.0)
+    for k in range(1, 64):
+        blocks[:, :, int(nat_of_pos[k])] = (ac[k - 1].astype(np.int64) * int(qac[k - 1])).astype(np.int16).astype(np.float64)
+    return np.einsum("ux,abuv,vy->abxy", K, blocks.reshape(bh, bw, 8, 8), K)
+
+
+def jpeg_like_wrapping(bw, bh, seed, bit_depth=10, squeeze=1):
+    """the JPEG-transcode chain [DCT, Quantize] of a one-component picture (squeeze = 1: the writer adds the default Squeeze of the DC
+    plane like the CLI, so the DC plane reaches the dequantisation as an int32 product of the unsqueeze chain; squeeze = 0: all 64
+    planes reach it as untouched coded planes, the int16 form of k_dequant) whose coefficient * q leaves int16: DC samples -3000..3000 with q = 16, and in every block three AC coefficients of
+    -2000..2000 on channels with q = 20..60.  The inverse DCT's own store, round(double) into pixel_type (dct.h:289), is undefined
+    for a value outside int16, so the float64 outputs of every block -- computed from the int16 products the reference stores --
+    are asserted to stay inside +-32000 (two-dimensional basis functions are at most 0.2405: three wrapped AC products and the DC
+    term give at most 3 * 0.2405 * 32768 + (32767 + 4096) / 8 = 28 250)."""
+    rng = np.random.default_rng(seed)
+    maxval = (1 << bit_depth) - 1
+    qdc, qac = 16, rng.integers(20, 61, 63)
+    dc = rng.integers(-3000, 3001, (bh, bw), dtype=np.int32)
+    ac = np.zeros((63, bh, bw), np.int32)
+    for by in range(bh):
+        for bx in range(bw):
+            for k in rng.choice(63, 3, replace=False):
+                ac[k, by, bx] = rng.integers(-2000, 2001)
+    out = idct_outputs(dc, ac, qdc, qac, maxval)
+    assert np.abs(out).max() <= 32000.0, "a block leaves the range in which the reference's iDCT store is defined"
+    assert (np.abs(ac.astype(np.int64) * qac[:, None, None]) > 32767).any() and (np.abs(dc.astype(np.int64) * qdc) > 32767).any()
+    chans = [dict(w=bw, h=bh, hshift=3, vshift=3, hcshift=int(DCT_CSHIFTS[0]), vcshift=int(DCT_CSHIFTS[0]), component=0, q=qdc, data=dc)]
+    for k in range(1, 64):
+        chans.append(dict(w=bw, h=bh, hshift=3, vshift=3, hcshift=int(DCT_CSHIFTS[k]), vcshift=int(DCT_CSHIFTS[k]), component=0, q=int(qac[k - 1]),
+                          data=ac[k - 1], predictor0=True))
+    return encode_channels(chans, bw * 8, bh * 8, 1, bit_depth, [TR_DCT, 0, TR_QUANTIZE, 0], squeeze=squeeze)
+
+
+# `ycocg` / `dct`: the planner switches that apply to the case (FUIFGPU_FUSE_YCOCG; FUIFGPU_FUSE_DEQUANT).
+# The comment beside a wrapping case = post-transform samples on which the int32 inverse chain (the oracle before the int16 stores were
+# matched) differed from the real reference, of the case's post-transform samples.
+CASES = [
+    # three levels h, v, h; 40x24: k_inv_hsqueeze_rows and the tail loops of the vertical kernel
+    dict(name="squeeze3_14bit_40x24", make=squeeze_only, args=dict(w=40, h=24, avg_max=16383, res_max=16383, seed=7101), wraps=True),        # 45 of 960 (4.7 %)
+    dict(name="squeeze3_15bit_40x24", make=squeeze_only, args=dict(w=40, h=24, avg_max=32767, res_max=16383, seed=7102), wraps=True),        # 461 of 960 (48.0 %)
+    # 262x140: k_inv_hsqueeze_tiles with three row tiles (the last of 12 rows), 131 residual columns (4 tiles of 32 pairs + a tail), 65 columns at
+    # the third level (k_inv_hsqueeze_rows, one step + a tail), a vertical step of 70 row pairs (8 steps of VS_STEP + a tail)
+    dict(name="squeeze3_14bit_262x140", make=squeeze_only, args=dict(w=262, h=140, avg_max=16383, res_max=16383, seed=7103), wraps=True),    # 1655 of 36 680 (4.5 %)
+    dict(name="squeeze3_15bit_262x140", make=squeeze_only, args=dict(w=262, h=140, avg_max=32767, res_max=16383, seed=7104), wraps=True),    # 17 268 of 36 680 (47.1 %)
+    # k_inv_hsq2_ycocg: 35 and 67 residual columns (2 and 4 tiles of 16 pairs + a tail of 3), 66 and 70 rows (two row tiles, the second of 2 and 6 rows)
+    dict(name="ycocg_squeeze_70x66", make=ycocg_squeeze, args=dict(w=70, h=66, seed=7201), wraps=True, ycocg=True),                          # 6847 of 13 860 (49.4 %)
+    dict(name="ycocg_squeeze_134x70", make=ycocg_squeeze, args=dict(w=134, h=70, seed=7202), wraps=True, ycocg=True),                        # 13 913 of 28 140 (49.4 %)
+    dict(name="quantize_q9_5000_40x24", make=quantize_only, args=dict(w=40, h=24, q=9, amp=5000, seed=7301), wraps=True),                    # 604 of 960 (62.9 %)
+    dict(name="quantize_q9_3640_40x24", make=quantize_only, args=dict(w=40, h=24, q=9, amp=3640, seed=7302), wraps=False),                   # 9 * 3640 = 32 760: the control, 0 of 960
+    dict(name="approximate_q9_5000_40x24", make=approximate, args=dict(w=40, h=24, q=9, amp=5000, rem=16383, seed=7501), wraps=True),   # 403 of 960 (42.0 %)
+    dict(name="soft_match_40x24", make=soft_match, args=dict(w=40, h=24, amp=16383, seed=7601), wraps=True),                                 # 168 of 960 (17.5 %)
+    dict(name="soft_match_chain_33x50", make=soft_match, args=dict(w=33, h=50, amp=0, seed=7602, chain=True), wraps=True),                      # 1139 of 1650 (69.0 %)
+    dict(name="jpeg_like_wrapping_12x10_blocks", make=jpeg_like_wrapping, args=dict(bw=12, bh=10, seed=7401), wraps=True, dct=True),         # 3972 of 7680 (51.7 %)
+    dict(name="jpeg_like_wrapping_6x5_blocks_dc_coded", make=jpeg_like_wrapping, args=dict(bw=6, bh=5, seed=7402, squeeze=0), wraps=True, dct=True),  # 1236 of 1920 (64.4 %)
+]
+
+
+def build(case):
+    return case["make"](**case["args"])

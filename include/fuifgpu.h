@@ -238,7 +238,12 @@ int fuifgpu_dev_download(void *dst_host, const void *src_device, size_t bytes); 
  * These are what Transform::apply(image, true) (transform/transform.cpp:48-63) dispatches to in the C++ boundary
  * layer (fuif_amd/boundary/fuif_gpu_boundary.cpp binds Transform::apply for the Squeeze, YCoCg, YCbCr, DCT, Quantize and
  * ChromaSubsample inverses to them: the path of Image::undo_transforms(keep != 0)); tests/test_gpu_transform_exports.py
- * checks each against the oracle. */
+ * checks each against the oracle.
+ * Sample contract: the reference's samples are pixel_type = int16_t (image/image.h:35).  The planes here are int32 containers of
+ * such samples: every input sample is an int16 value widened (what the binding copies out of a Channel), and the Squeeze, Quantize,
+ * Approximate and soft 2D-match inverses store what the reference's assignment to pixel_type keeps -- the low 16 bits of the int
+ * result, sign-extended (squeeze.h:103-107, quantize.h:41, approximate.h:53-55, 2dmatch.h:129,155) -- so every output is again an
+ * int16 value widened.  Inputs outside that range are outside the contract. */
 /* transform/squeeze.h:81-132 inv_hsqueeze: avg w1 x h + residual w2 x h -> out (w1+w2) x h */
 int fuifgpu_inv_hsqueeze(const int32_t *avg, int w1, const int32_t *res, int w2, int h, int32_t *out, int n_planes,
                          int64_t avg_stride, int64_t res_stride, int64_t out_stride, void *stream);
@@ -249,7 +254,7 @@ int fuifgpu_inv_vsqueeze(const int32_t *avg, int h1, const int32_t *res, int h2,
 int fuifgpu_inv_ycocg(int32_t *c0, int32_t *c1, int32_t *c2, int w, int h, int p0, int p1, int p2, int maxval, void *stream);
 /* transform/ycbcr.h:33-63 inv_YCbCr */
 int fuifgpu_inv_ycbcr(int32_t *c0, int32_t *c1, int32_t *c2, int w, int h, int p0, int p1, int p2, int minval, int maxval, void *stream);
-/* transform/quantize.h:32-49 inv_quantize of one plane: every sample times the channel's quantisation constant, in place */
+/* transform/quantize.h:32-49 inv_quantize of one plane: every sample times the channel's quantisation constant, stored as int16, in place */
 int fuifgpu_inv_quantize(int32_t *plane, int64_t n_samples, int q, void *stream);
 /* transform/dct.h:88-107 + 282-291: 64 coefficient planes (bw x bh each, src[i] in the
  * reference's own zig-zag position order i=0..63) -> (8bw) x (8bh) samples; DC offset (maxval+1)*4 */
@@ -259,7 +264,8 @@ int fuifgpu_upsample(const int32_t *in, int w, int h, int srh, int srv, int32_t 
 /* transform/palette.h:57-64 inv_palette, one component per call: out[i] = palette_row[CLAMP(index[i], 0, colours-1)] over w x h samples
  * (palette_row = row `component` of the palette meta-channel; colours == 0 reads Channel::zero, image.h:82). out may not be index. */
 int fuifgpu_inv_palette(const int32_t *index, int w, int h, const int32_t *palette_row, int colours, int32_t *out, void *stream);
-/* transform/approximate.h:44-57 inv_approximate of one channel, in place: plane[i] = plane[i] * q + remainder[i] (q = parameter + 1);
+/* transform/approximate.h:44-57 inv_approximate of one channel, in place: plane[i] = plane[i] * q + remainder[i] (q = parameter + 1), the product
+ * and the sum each stored as int16;
  * remainder == NULL = "the remainder channel is not available" (:49,54): nothing is added */
 int fuifgpu_inv_approximate(int32_t *plane, const int32_t *remainder, int64_t n_samples, int q, void *stream);
 /* transform/2dmatch.h:112-177 inv_match, in place on n_planes (<= 64) w x h planes; match = the match meta-channel, match_q / match_maxval its

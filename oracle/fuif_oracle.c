@@ -279,8 +279,10 @@ static void ch_setzero(fo_channel *c) {
 }
 /* A stored sample is the reference's pixel_type = int16_t (image/image.h:35): what the entropy decoder stores -- decoded samples, the
  * fill of a constant plane, the `zero` a resize fills with -- is narrowed like an assignment to pixel_type narrows it.  No effect on
- * valid streams (check_bit_depth, encoding.cpp:61-72, caps compressed samples at 15 bits of magnitude); on damaged ones an uncompressed
- * group or a constant plane can name a larger value, and the product's coefficient slab holds int16 samples as well. */
+ * what valid streams code (check_bit_depth, encoding.cpp:61-72, caps compressed samples at 15 bits of magnitude); on damaged ones an
+ * uncompressed group or a constant plane can name a larger value, and the product's coefficient slab holds int16 samples as well.
+ * The inverse transforms narrow the same way wherever the reference assigns to a pixel_type (Squeeze, Quantize, Approximate, soft 2D
+ * match: cited at each place below) -- valid streams do reach those: fuif_amd/edgecases.py, tests/test_oracle_vs_ref.py. */
 static inline int32_t px(int v) { return (int32_t)(int16_t)v; }
 /* image/image.h:73-79 resize(): data.resize(w*h, zero) keeps existing leading samples */
 static void ch_materialize(fo_channel *c) {
@@ -1293,17 +1295,20 @@ fo_image *fo_decode(const uint8_t *blob, size_t n, int preview, int io_kind, int
 /* ------------------------------------------------------------------------------------------- */
 /* inverse transforms                                                                           */
 
-/* transform/squeeze.h:61-77 */
+/* transform/squeeze.h:61-77.  The parameters, `diff` and the result are pixel_type there (:61-62): the arithmetic runs in promoted int and
+ * every assignment to diff narrows (px).  For int16 arguments no assignment changes a value (tests/test_squeeze_arith.py); stated anyway,
+ * this file restates the reference. */
 int fo_smooth_tendency(int B, int a, int n) {
-    int diff = 0;
+    B = px(B); a = px(a); n = px(n);                                            /* squeeze.h:61 pixel_type parameters */
+    int diff = 0;                                                               /* squeeze.h:62 pixel_type diff */
     if (B >= a && a >= n) {
-        diff = (4 * B - 3 * n - a + 6) / 12;
-        if (diff - (diff & 1) > 2 * (B - a)) diff = 2 * (B - a) + 1;
-        if (diff + (diff & 1) > 2 * (a - n)) diff = 2 * (a - n);
+        diff = px((4 * B - 3 * n - a + 6) / 12);                                /* squeeze.h:64 */
+        if (diff - (diff & 1) > 2 * (B - a)) diff = px(2 * (B - a) + 1);        /* squeeze.h:67 */
+        if (diff + (diff & 1) > 2 * (a - n)) diff = px(2 * (a - n));            /* squeeze.h:68 */
     } else if (B <= a && a <= n) {
-        diff = (4 * B - 3 * n - a - 6) / 12;
-        if (diff + (diff & 1) < 2 * (B - a)) diff = 2 * (B - a) - 1;
-        if (diff - (diff & 1) < 2 * (a - n)) diff = 2 * (a - n);
+        diff = px((4 * B - 3 * n - a - 6) / 12);                                /* squeeze.h:70 */
+        if (diff + (diff & 1) < 2 * (B - a)) diff = px(2 * (B - a) - 1);        /* squeeze.h:73 */
+        if (diff - (diff & 1) < 2 * (a - n)) diff = px(2 * (a - n));            /* squeeze.h:74 */
     }
     return diff;
 }
@@ -1318,10 +1323,12 @@ static void chout_from(fo_channel *o, const fo_channel *in, int w, int h) {
     o->data = (int32_t *)calloc(want ? want : 1, sizeof(int32_t));
     o->size = want;
 }
-/* checked store, image.h:84-85 (out-of-range stores land in `zero`, i.e. are dropped) */
+/* checked store, image.h:84-85 (out-of-range stores land in `zero`, i.e. are dropped).  Channel::value() hands out a pixel_type &
+ * (image.h:84; data is std::vector<pixel_type>, :56, and zero a pixel_type, :59): whatever an inverse transform assigns through it
+ * is narrowed to int16 */
 static inline void ch_store(fo_channel *c, int r, int col, int v) {
     size_t idx = (size_t)((int64_t)r * c->w + col);
-    if (idx < c->size) { if (!c->data) ch_materialize(c); c->data[idx] = v; } else c->zero = v;
+    if (idx < c->size) { if (!c->data) ch_materialize(c); c->data[idx] = px(v); } else c->zero = px(v);
 }
 
 /* transform/squeeze.h:81-132 */
@@ -1332,12 +1339,13 @@ static void inv_hsqueeze(fo_image *img, int c, int rc) {
     chout_from(&out, chin, chin->w + res->w, chin->h);
     out.hshift = chin->hshift - 1; out.hcshift = chin->hcshift - 1;
     for (int y = 0; y < chin->h; y++) {
-        int avg = ch_value(chin, y, 0);
-        int next_avg = (1 < chin->w ? ch_value(chin, y, 1) : avg);
-        int tendency = fo_smooth_tendency(avg, avg, next_avg);
-        int diff = ch_value(res, y, 0) + tendency;
-        int A = ((avg << 1) + diff + (diff > 0 ? -(diff & 1) : (diff & 1))) >> 1;
-        int B = A - diff;
+        /* avg, next_avg, tendency, diff, A, B, left are all pixel_type in the reference (squeeze.h:89-94,98-107): px() at each assignment */
+        int avg = ch_value(chin, y, 0);                                                          /* squeeze.h:89 */
+        int next_avg = (1 < chin->w ? ch_value(chin, y, 1) : avg);                               /* squeeze.h:90 */
+        int tendency = fo_smooth_tendency(avg, avg, next_avg);                                   /* squeeze.h:91 */
+        int diff = px(ch_value(res, y, 0) + tendency);                                           /* squeeze.h:92 */
+        int A = px(((avg << 1) + diff + (diff > 0 ? -(diff & 1) : (diff & 1))) >> 1);            /* squeeze.h:93 */
+        int B = px(A - diff);                                                                    /* squeeze.h:94 */
         ch_store(&out, y, 0, A);
         ch_store(&out, y, 1, B);
         for (int x = 1; x < res->w; x++) {
@@ -1346,10 +1354,10 @@ static void inv_hsqueeze(fo_image *img, int c, int rc) {
             next_avg = (x + 1 < chin->w ? ch_value(chin, y, x + 1) : avg);
             int left = out.data[(size_t)y * out.w + (x << 1) - 1];
             tendency = fo_smooth_tendency(left, avg, next_avg);
-            diff = dmt + tendency;
-            A = ((avg << 1) + diff + (diff > 0 ? -(diff & 1) : (diff & 1))) >> 1;
+            diff = px(dmt + tendency);                                                           /* squeeze.h:103 */
+            A = px(((avg << 1) + diff + (diff > 0 ? -(diff & 1) : (diff & 1))) >> 1);            /* squeeze.h:105 */
             ch_store(&out, y, x << 1, A);
-            B = A - diff;
+            B = px(A - diff);                                                                    /* squeeze.h:107 */
             ch_store(&out, y, (x << 1) + 1, B);
         }
         if (out.w & 1) ch_store(&out, y, out.w - 1, ch_value(chin, y, chin->w - 1));
@@ -1371,10 +1379,10 @@ static void inv_vsqueeze(fo_image *img, int c, int rc) {
         int next_avg = avg;
         if (1 < chin->h) next_avg = ch_value(chin, 1, x);
         int tendency = fo_smooth_tendency(avg, avg, next_avg);
-        int diff = dmt + tendency;
-        int A = ((avg << 1) + diff + (diff > 0 ? -(diff & 1) : (diff & 1))) >> 1;
+        int diff = px(dmt + tendency);                                                           /* squeeze.h:189 pixel_type diff */
+        int A = px(((avg << 1) + diff + (diff > 0 ? -(diff & 1) : (diff & 1))) >> 1);            /* squeeze.h:191 pixel_type A */
         ch_store(&out, 0, x, A);
-        int B = A - diff;
+        int B = px(A - diff);                                                                    /* squeeze.h:193 pixel_type B */
         ch_store(&out, 1, x, B);
     }
     for (int y = 1; y < res->h; y++) {
@@ -1385,10 +1393,10 @@ static void inv_vsqueeze(fo_image *img, int c, int rc) {
             if (y + 1 < chin->h) next_avg = ch_value(chin, y + 1, x);
             int top = out.data[(size_t)((y << 1) - 1) * out.w + x];
             int tendency = fo_smooth_tendency(top, avg, next_avg);
-            int diff = dmt + tendency;
-            int A = ((avg << 1) + diff + (diff > 0 ? -(diff & 1) : (diff & 1))) >> 1;
+            int diff = px(dmt + tendency);                                                       /* squeeze.h:209 pixel_type diff */
+            int A = px(((avg << 1) + diff + (diff > 0 ? -(diff & 1) : (diff & 1))) >> 1);        /* squeeze.h:211 pixel_type A */
             ch_store(&out, y << 1, x, A);
-            int B = A - diff;
+            int B = px(A - diff);                                                                /* squeeze.h:213 pixel_type B */
             ch_store(&out, (y << 1) + 1, x, B);
         }
     }
@@ -1475,8 +1483,8 @@ static int inv_quantize(fo_image *img) {
         int q = ch->q;
         if (q == 1) continue;
         for (int y = 0; y < ch->h; y++)
-            for (int x = 0; x < ch->w; x++) ch_store(ch, y, x, ch_value(ch, y, x) * q);
-        ch->minval *= q; ch->maxval *= q; ch->q = 1;
+            for (int x = 0; x < ch->w; x++) ch_store(ch, y, x, ch_value(ch, y, x) * q);   /* quantize.h:41: `*=` on a pixel_type &, narrowed by ch_store */
+        ch->minval = px(ch->minval * q); ch->maxval = px(ch->maxval * q); ch->q = 1;     /* quantize.h:44-45: Channel::minval / maxval are pixel_type (image.h:58) */
     }
     return 1;
 }
@@ -1654,7 +1662,8 @@ static int inv_approximate(fo_image *img, const fo_transform *t) {
             for (int x = 0; x < ch->w; x++) {
                 size_t at = (size_t)y * ch->w + x;
                 if (at >= ch->size) continue;
-                ch->data[at] = ch->data[at] * q + (have ? ch_value(chr, y, x) : 0);
+                ch->data[at] = px(ch->data[at] * q);                                  /* approximate.h:53: `*= q` on a pixel_type & */
+                ch->data[at] = px(ch->data[at] + (have ? ch_value(chr, y, x) : 0));   /* approximate.h:55: `+=` on a pixel_type & */
             }
     }
     img_erase_channels(img, offset, img->nch - offset);
@@ -1710,7 +1719,7 @@ static int inv_match(fo_image *img, fo_transform *t) {
                 int32_t zs_a, zs_b;
                 int32_t *dst = ch_slot(ch, y, x, &zs_a);
                 int32_t src = *ch_slot(ch, y + yo, x + xo, &zs_b);
-                if (softmatch) *dst += src; else *dst = src;
+                if (softmatch) *dst = px(*dst + src); else *dst = src;   /* 2dmatch.h:129,155: `+=` on a pixel_type & */
             }
         }
     img->nb_meta_channels--;

@@ -103,6 +103,44 @@ def test_inv_vsqueeze_export(glib, olib, h1, h2, w):
         assert np.array_equal(got[p], ref_squeeze(olib, False, avg[p], res[p].reshape(h2, w)))
 
 
+def _int16_planes(rng, shape):
+    """the whole int16 range, every other sample near one of its ends (where sums leave 16 bits)"""
+    d = rng.integers(-32768, 32768, shape, dtype=np.int32)
+    ends = np.where(rng.integers(0, 2, shape) == 1, 32767 - rng.integers(0, 4096, shape), -32768 + rng.integers(0, 4096, shape)).astype(np.int32)
+    return np.where(rng.integers(0, 2, shape) == 1, ends, d).astype(np.int32)
+
+
+# (the loop-boundary widths of test_inv_hsqueeze_export, and heights on both sides of the 64-row tiles of k_inv_hsqueeze_tiles)
+@pytest.mark.parametrize("w1,w2,h", [(4, 3, 1), (1, 1, 3), (33, 32, 7), (32, 31, 2), (34, 33, 5), (64, 64, 65), (65, 64, 130), (97, 96, 70), (129, 128, 3), (161, 160, 1)])
+def test_inv_hsqueeze_export_full_int16_range(glib, olib, w1, w2, h):
+    """averages and residuals drawn from the whole int16 range: diff, A and B leave 16 bits and are stored the way the reference's
+    pixel_type variables keep them (squeeze.h:98-108); the oracle's restatement narrows at the same places and is pinned to the real
+    reference in tests/test_oracle_vs_ref.py"""
+    rng = np.random.default_rng(77000 + w1 * 1000 + h)
+    n_planes = 2
+    avg, res = _int16_planes(rng, (n_planes, h, w1)), _int16_planes(rng, (n_planes, h, w2))
+    d_avg, d_res, d_out = Dev(avg), Dev(res), Dev(np.zeros((n_planes, h, w1 + w2), np.int32))
+    assert glib.fuifgpu_inv_hsqueeze(d_avg.ptr, w1, d_res.ptr, w2, h, d_out.ptr, n_planes, h * w1, h * w2, h * (w1 + w2), None) == 0
+    got = d_out.get().reshape(n_planes, h, w1 + w2)
+    assert got.min() >= -32768 and got.max() <= 32767
+    for p in range(n_planes):
+        assert np.array_equal(got[p], ref_squeeze(olib, True, avg[p], res[p]))
+
+
+@pytest.mark.parametrize("h1,h2,w", [(4, 3, 1), (1, 1, 3), (33, 32, 7), (8, 8, 5), (9, 8, 5), (9, 9, 2), (17, 16, 3), (65, 64, 300), (70, 70, 131)])
+def test_inv_vsqueeze_export_full_int16_range(glib, olib, h1, h2, w):
+    """as above for the vertical kernel: heights on both sides of its VS_STEP = 8 loop, more than one 256-lane block of columns"""
+    rng = np.random.default_rng(78000 + h1 * 1000 + w)
+    n_planes = 2
+    avg, res = _int16_planes(rng, (n_planes, h1, w)), _int16_planes(rng, (n_planes, h2, w))
+    d_avg, d_res, d_out = Dev(avg), Dev(res), Dev(np.zeros((n_planes, h1 + h2, w), np.int32))
+    assert glib.fuifgpu_inv_vsqueeze(d_avg.ptr, h1, d_res.ptr, h2, w, d_out.ptr, n_planes, h1 * w, h2 * w, (h1 + h2) * w, None) == 0
+    got = d_out.get().reshape(n_planes, h1 + h2, w)
+    assert got.min() >= -32768 and got.max() <= 32767
+    for p in range(n_planes):
+        assert np.array_equal(got[p], ref_squeeze(olib, False, avg[p], res[p]))
+
+
 def test_squeeze_known_answers(glib, olib):
     """SURVEY.md Appendix E.4 (real reference): averages [100,104,90,91] + residuals [3,-2,5] -> 101 99 103 105 92 87 91,
     as a row (horizontal) and as a column (vertical)"""
@@ -194,6 +232,19 @@ def test_inv_quantize_export(glib, n, q):
     assert np.array_equal(d.get(), a * q)
 
 
+@pytest.mark.parametrize("n,q", [(1, 7), (1000, 3), (257 * 33, 16), (64 * 256 + 5, 255)])
+def test_inv_quantize_export_full_int16_range(glib, n, q):
+    """quantize.h:41 is `ch.value(y,x) *= q` on a pixel_type &: the int product, stored as int16 (numpy: int64 product, cast to int16)"""
+    rng = np.random.default_rng(79000 + n + q)
+    a = _int16_planes(rng, n)
+    d = Dev(a)
+    assert glib.fuifgpu_inv_quantize(d.ptr, n, q, None) == 0
+    _sync()
+    want = (a.astype(np.int64) * q).astype(np.int16).astype(np.int32)
+    assert (np.abs(a.astype(np.int64) * q) > 32767).any()
+    assert np.array_equal(d.get(), want)
+
+
 @pytest.mark.parametrize("w,h,srh,srv", [(1, 1, 2, 2), (5, 3, 2, 2), (64, 17, 2, 1), (33, 40, 1, 2), (240, 135, 2, 2)])
 def test_upsample_export(glib, olib, w, h, srh, srv):
     rng = np.random.default_rng(w * 3 + h + srh)
@@ -230,6 +281,20 @@ def test_inv_approximate_export(glib, n, q, have):
     assert np.array_equal(d.get(), a * q + (r if have else 0))
 
 
+@pytest.mark.parametrize("n,q,have", [(1, 2, True), (1000, 4, True), (257 * 33, 10, False), (64 * 256 + 5, 9, True)])
+def test_inv_approximate_export_full_int16_range(glib, n, q, have):
+    """approximate.h:53-55: `*= q`, then `+=`, each on a pixel_type &: the product is stored as int16 before the remainder is added,
+    and the sum is stored as int16"""
+    rng = np.random.default_rng(80000 + n + q)
+    a, r = _int16_planes(rng, n), _int16_planes(rng, n)
+    d, dr = Dev(a), Dev(r)
+    assert glib.fuifgpu_inv_approximate(d.ptr, dr.ptr if have else None, n, q, None) == 0
+    _sync()
+    prod = (a.astype(np.int64) * q).astype(np.int16).astype(np.int64)
+    want = (prod + (r if have else 0)).astype(np.int16).astype(np.int32)
+    assert np.array_equal(d.get(), want)
+
+
 def _match_case(rng, w, h, n_planes, maxz, density):
     z = rng.integers(1, maxz + 1, (h, w), dtype=np.int32)
     z[rng.random((h, w)) >= density] = 0
@@ -241,7 +306,9 @@ def _match_case(rng, w, h, n_planes, maxz, density):
 @pytest.mark.parametrize("w,h,n_planes,maxz,density", [(40, 30, 3, 24, 0.5), (64, 64, 1, 60, 0.9), (97, 13, 4, 12, 0.2), (33, 50, 2, 1, 1.0)])
 def test_inv_match_free_offsets_export(glib, olib, w, h, n_planes, maxz, density, soft):
     """transform/2dmatch.h:136-146 (match channel q == 1): every matched sample copies (soft: adds) an EARLIER sample, which may
-    itself be matched -- chains up to the whole row long at density 1.0 -- incl. sources before the first sample (Channel::zero)"""
+    itself be matched -- chains up to the whole row long at density 1.0 -- incl. sources before the first sample (Channel::zero).
+    A soft chain's running sum passes 16 bits at density 1.0 (maxz 1: one chain through the whole plane): every link is stored as the
+    reference's pixel_type (2dmatch.h:129), which the oracle restates and fuif_amd/edgecases.py's soft_match_chain_33x50 pins to the real reference"""
     rng = np.random.default_rng(w * 31 + h + maxz + soft)
     z, planes = _match_case(rng, w, h, n_planes, maxz, density)
     want = planes.copy()

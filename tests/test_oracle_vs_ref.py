@@ -4,6 +4,7 @@ Image::undo_transforms(), FileIO and BlobReader end-of-file semantics, previews 
 import numpy as np
 import pytest
 
+from fuif_amd import edgecases
 from fuif_amd.synth import photographic
 
 META = ("w", "h", "minval", "maxval", "q", "hshift", "vshift", "hcshift", "vcshift", "component", "size")
@@ -47,3 +48,25 @@ def test_port_equals_reference(port, ref, case):
         cut = blob[: max(8, int(len(blob) * frac))]
         a, b = ref.decode(cut), port.decode(cut)
         same(a, b)
+
+
+@pytest.mark.parametrize("case", edgecases.CASES, ids=lambda c: c["name"])
+def test_port_equals_reference_at_the_int16_edges(port, ref, case):
+    """hand-made valid streams whose inverse-transform intermediates leave 16 bits (fuif_amd/edgecases.py): the reference stores
+    every sample, and Channel::minval / maxval, as pixel_type = int16_t (image/image.h:35,58) and narrows what Squeeze and Quantize
+    compute (squeeze.h:92-107,189-213, quantize.h:41,44-45); the restatement must store the same -- planes and channel metadata,
+    before and after undo_transforms, with both I/O kinds"""
+    blob = edgecases.build(case)
+    for io_kind in (0, 1):
+        a0, a1 = ref.decode_both(blob, io_kind=io_kind)
+        b0, b1 = port.decode_both(blob, io_kind=io_kind)
+        assert a0.ok and a1.ok, "the real reference must accept the stream"
+        same(a0, b0)
+        same(a1, b1)
+    if case["wraps"]:
+        # the case does what it is for: some post-transform sample is not what 32-bit arithmetic on the coded planes gives -- shown where it is
+        # cheap to restate, the Quantize-only stream (quantize.h:41 on the one coded plane)
+        if case["make"] is edgecases.quantize_only:
+            wide = a0.channels[0]["data"].astype(np.int64) * case["args"]["q"]
+            assert (np.abs(wide) > 32767).any()
+            assert np.array_equal(a1.channels[0]["data"], np.clip(wide.astype(np.int16), 0, 16383))
