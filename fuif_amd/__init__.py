@@ -91,6 +91,17 @@ class EncodeOptions(C.Structure):
                 ("max_tree_nodes", C.c_int32), ("emit_index", C.c_int32), ("split_bits", C.c_int32), ("gpu_forward", C.c_int32), ("gpu_entropy", C.c_int32)]
 
 
+class LossyOptions(C.Structure):
+    """fuifgpu_lossy_options (include/fuifgpu.h): what `fuif -Q quality[,chroma_quality]` sets; versioned by its first field"""
+    _fields_ = [("struct_size", C.c_uint32), ("quality", C.c_float), ("chroma_quality", C.c_float)]
+
+
+def make_lossy_options(quality=None, chroma_quality=None):
+    """LossyOptions for the two keywords of encode_image / encode_images: a missing quality is 100 (lossless luma), a missing
+    chroma quality "same as quality" (the CLI's default, 101)"""
+    return LossyOptions(C.sizeof(LossyOptions), 100.0 if quality is None else float(quality), 101.0 if chroma_quality is None else float(chroma_quality))
+
+
 def make_encode_options(*fields):
     """EncodeOptions with struct_size set, the fields behind it in header order"""
     return EncodeOptions(C.sizeof(EncodeOptions), *fields)
@@ -104,10 +115,11 @@ ABI_SYMBOLS = [
     "fuifgpu_batch_decode", "fuifgpu_batch_undo_transforms", "fuifgpu_batch_sync", "fuifgpu_batch_status",
     "fuifgpu_batch_create_streaming", "fuifgpu_batch_undo_transforms_to", "fuifgpu_batch_channel_meta", "fuifgpu_batch_coef_ptr", "fuifgpu_batch_out_ptr", "fuifgpu_batch_download_coef",
     "fuifgpu_batch_download_out", "fuifgpu_batch_last_timing", "fuifgpu_batch_profile", "fuifgpu_batch_tile_log", "fuifgpu_batch_sched_stats", "fuifgpu_inv_hsqueeze", "fuifgpu_inv_vsqueeze",
-    "fuifgpu_inv_ycocg", "fuifgpu_inv_ycbcr", "fuifgpu_inv_quantize", "fuifgpu_idct8x8", "fuifgpu_upsample", "fuifgpu_inv_palette", "fuifgpu_inv_approximate", "fuifgpu_inv_match", "fuifgpu_fwd_ycocg", "fuifgpu_fwd_hsqueeze", "fuifgpu_fwd_vsqueeze", "fuifgpu_encode_image", "fuifgpu_encode_channels", "fuifgpu_free_blob",
+    "fuifgpu_inv_ycocg", "fuifgpu_inv_ycbcr", "fuifgpu_inv_quantize", "fuifgpu_idct8x8", "fuifgpu_upsample", "fuifgpu_inv_palette", "fuifgpu_inv_approximate", "fuifgpu_inv_match", "fuifgpu_fwd_ycocg", "fuifgpu_fwd_hsqueeze", "fuifgpu_fwd_vsqueeze", "fuifgpu_fwd_quantize", "fuifgpu_encode_image", "fuifgpu_encode_channels", "fuifgpu_free_blob",
     "fuifgpu_index_parse", "fuifgpu_index_append", "fuifgpu_batch_group_index", "fuifgpu_batch_set_group_parallel",
     "fuifgpu_plan_packed_bytes", "fuifgpu_batch_pack_out", "fuifgpu_batch_download_packed",
     "fuifgpu_dev_alloc", "fuifgpu_dev_free", "fuifgpu_dev_upload", "fuifgpu_dev_download",
+    "fuifgpu_encode_image_lossy", "fuifgpu_encode_images_lossy", "fuifgpu_quantization_constant",
     "fuifgpu_plane_checksums", "fuifgpu_device_count", "fuifgpu_set_device", "fuifgpu_get_device", "fuifgpu_batch_device", "fuifgpu_peer_copy", "fuifgpu_batch_set_in_flight",
 ]
 
@@ -201,6 +213,14 @@ def lib():
     L.fuifgpu_fwd_ycocg.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
     L.fuifgpu_fwd_hsqueeze.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
     L.fuifgpu_fwd_vsqueeze.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+    L.fuifgpu_dev_alloc.argtypes = [C.c_size_t]; L.fuifgpu_dev_alloc.restype = vp
+    L.fuifgpu_dev_free.argtypes = [vp]; L.fuifgpu_dev_free.restype = None
+    L.fuifgpu_dev_upload.argtypes = [vp, vp, C.c_size_t]
+    L.fuifgpu_dev_download.argtypes = [vp, vp, C.c_size_t]
+    L.fuifgpu_fwd_quantize.argtypes = [vp, C.c_int64, C.c_int, vp, vp]
+    L.fuifgpu_encode_image_lossy.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.fuifgpu_encode_images_lossy.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.fuifgpu_quantization_constant.argtypes = [C.c_float, C.c_float, C.c_int, C.c_int, C.c_int]
     L.fuifgpu_encode_image.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.fuifgpu_encode_images.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.fuifgpu_free_blob.argtypes = [vp]; L.fuifgpu_free_blob.restype = None
@@ -468,8 +488,10 @@ DEFAULT_SPLIT_BITS = 0
 
 
 def encode_image(planes, bit_depth=8, ycocg=True, squeeze=True, max_properties=12, tree_mode=1, max_tree_nodes=4095, index=False,
-                 split_bits=None, gpu_forward=False, gpu_entropy=False):
-    """(C,H,W) int32 planes -> lossless .fuif bytes (host C++ writer, csrc/writer.cpp).
+                 split_bits=None, gpu_forward=False, gpu_entropy=False, quality=None, chroma_quality=None):
+    """(C,H,W) int32 planes -> .fuif bytes (host C++ writer, csrc/writer.cpp); lossless unless a quality is given.
+    quality / chroma_quality: the two numbers of `fuif -Q` (0..100; chroma_quality None or > 100 = same as quality): the channels are
+    quantised after YCoCg and Squeeze with the reference CLI's constants (fuifgpu_encode_image_lossy); 100 writes the lossless bytes.
     index=True appends the group index trailer (csrc/index.cpp) that unlocks one-wavefront-per-group decoding.
     gpu_forward=True runs the forward YCoCg and Squeeze on the GPU (fuifgpu_fwd_*), gpu_entropy=True the MANIAC pixel loop of
     every compressed group (csrc/maniac_encode.hip): same bytes either way."""
@@ -479,16 +501,21 @@ def encode_image(planes, bit_depth=8, ycocg=True, squeeze=True, max_properties=1
     opt = make_encode_options(int(ycocg), int(squeeze), max_properties, tree_mode, max_tree_nodes, int(index), int(split_bits), int(gpu_forward), int(gpu_entropy))
     out = C.c_void_p()
     n = C.c_size_t(0)
-    _check(lib().fuifgpu_encode_image(planes.ctypes.data, w, h, c, bit_depth, C.byref(opt), C.byref(out), C.byref(n)))
+    if quality is None and chroma_quality is None:
+        _check(lib().fuifgpu_encode_image(planes.ctypes.data, w, h, c, bit_depth, C.byref(opt), C.byref(out), C.byref(n)))
+    else:
+        lossy = make_lossy_options(quality, chroma_quality)
+        _check(lib().fuifgpu_encode_image_lossy(planes.ctypes.data, w, h, c, bit_depth, C.byref(opt), C.byref(lossy), C.byref(out), C.byref(n)))
     blob = C.string_at(out.value, n.value)
     lib().fuifgpu_free_blob(out)
     return blob
 
 
 def encode_images(images, bit_depth=8, ycocg=True, squeeze=True, max_properties=12, tree_mode=1, max_tree_nodes=4095, index=False,
-                  split_bits=None, gpu_forward=False):
+                  split_bits=None, gpu_forward=False, quality=None, chroma_quality=None):
     """a batch of equally sized (C,H,W) pictures -> list of .fuif byte strings, what encode_image writes for each of them; the
-    MANIAC pixel loops of ALL their channel groups run in one launch pair on the GPU (fuifgpu_encode_images)"""
+    MANIAC pixel loops of ALL their channel groups run in one launch pair on the GPU (fuifgpu_encode_images; with a quality,
+    fuifgpu_encode_images_lossy)"""
     split_bits = DEFAULT_SPLIT_BITS if split_bits is None else split_bits
     arrs = [np.ascontiguousarray(im, dtype=np.int32) for im in images]
     c, h, w = arrs[0].shape
@@ -499,12 +526,30 @@ def encode_images(images, bit_depth=8, ycocg=True, squeeze=True, max_properties=
     ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
     outs = (C.c_void_p * n)()
     sizes = (C.c_size_t * n)()
-    _check(lib().fuifgpu_encode_images(ptrs, n, w, h, c, bit_depth, C.byref(opt), outs, sizes))
+    if quality is None and chroma_quality is None:
+        _check(lib().fuifgpu_encode_images(ptrs, n, w, h, c, bit_depth, C.byref(opt), outs, sizes))
+    else:
+        lossy = make_lossy_options(quality, chroma_quality)
+        _check(lib().fuifgpu_encode_images_lossy(ptrs, n, w, h, c, bit_depth, C.byref(opt), C.byref(lossy), outs, sizes))
     blobs = []
     for k in range(n):
         blobs.append(C.string_at(outs[k], sizes[k]))
         lib().fuifgpu_free_blob(C.c_void_p(outs[k]))
     return blobs
+
+
+def quantization_constant(quality, chroma_quality=None, squeeze=True, chroma_table=False, shift=0):
+    """the constant `fuif -Q quality[,chroma_quality]` gives a channel of hcshift + vcshift = shift (fuifgpu_quantization_constant)"""
+    q = lib().fuifgpu_quantization_constant(float(quality), 101.0 if chroma_quality is None else float(chroma_quality), int(bool(squeeze)), int(bool(chroma_table)), int(shift))
+    if q < 1:
+        _check(-q)
+    return q
+
+
+def fwd_quantize(plane_device_ptr, n_samples, q, minmax_device_ptr=None, stream=None):
+    """fuifgpu_fwd_quantize: n int32 samples in DEVICE memory divided by q in place (truncating); their {min, max} accumulated
+    into two int32 of device memory when a pointer is given"""
+    _check(lib().fuifgpu_fwd_quantize(plane_device_ptr, int(n_samples), int(q), minmax_device_ptr, stream))
 
 
 def index_parse(blob):

@@ -132,6 +132,36 @@ size_t maniac_scratch_bytes(int max_nodes, size_t *bfs_off, size_t *leaves_off, 
     *subtree_off = nodes + snodes + leaves + stack + queue;
     return nodes + snodes + leaves + stack + queue + up((size_t)(max_nodes + 1) * 2);
 }
+
+// The writer's forward Quantize of one picture (writer.cpp, gpu_forward): ONE device buffer holds the {min, max} pairs and behind them
+// the channel table, so it is one upload, one launch over every channel and one copy back for all the ranges.
+int fwd_quantize_channels_gpu(const QuantChan *channels, int n_channels, int32_t *minmax_host) {
+    if (n_channels <= 0) return FUIFGPU_OK;
+    const size_t pairs = ((size_t)n_channels * 2 * sizeof(int32_t) + 15) / 16 * 16;   // the table behind them starts 16-byte aligned
+    std::vector<uint8_t> host(pairs + sizeof(QuantChan) * (size_t)n_channels);
+    int32_t *mm = reinterpret_cast<int32_t *>(host.data());
+    QuantChan *table = reinterpret_cast<QuantChan *>(host.data() + pairs);
+    int total_blocks = 0;
+    for (int k = 0; k < n_channels; k++) {
+        mm[2 * k] = INT32_MAX; mm[2 * k + 1] = INT32_MIN;
+        if (channels[k].q < 1 || channels[k].n < 0 || channels[k].slot >= n_channels || (!channels[k].plane && channels[k].n > 0)) return FUIFGPU_E_ARG;
+        table[k] = channels[k];
+        table[k].first_block = total_blocks;
+        table[k].n_blocks = fwd_quantize_blocks(channels[k].n);
+        total_blocks += table[k].n_blocks;
+    }
+    uint8_t *dev = nullptr;
+    HIPCHK(hipMalloc((void **)&dev, host.size()));
+    hipError_t e = hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_fwd_quantize(reinterpret_cast<const QuantChan *>(dev + pairs), n_channels, total_blocks, reinterpret_cast<int32_t *>(dev), nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(minmax_host, dev, sizeof(int32_t) * 2 * (size_t)n_channels, hipMemcpyDeviceToHost);   // waits for the kernel
+    hipFree(dev);
+    if (e != hipSuccess) return hip_fail(e, "fwd_quantize_channels_gpu");
+    return FUIFGPU_OK;
+}
 }  // namespace fuifgpu
 
 extern "C" {
@@ -1042,6 +1072,12 @@ int fuifgpu_fwd_hsqueeze(const int32_t *in, int w, int h, int32_t *avg, int32_t 
 int fuifgpu_fwd_vsqueeze(const int32_t *in, int w, int h, int32_t *avg, int32_t *res, void *stream) {
     if (!in || !avg || (h > 1 && !res) || w < 1 || h < 1) return FUIFGPU_E_ARG;
     launch_fwd_squeeze(false, in, w, h, avg, res, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return FUIFGPU_OK;
+}
+int fuifgpu_fwd_quantize(int32_t *plane, int64_t n_samples, int q, int32_t *minmax_device, void *stream) {
+    if (q < 1 || n_samples < 0 || (!plane && n_samples > 0)) return FUIFGPU_E_ARG;
+    launch_fwd_quantize_plane(plane, n_samples, q, minmax_device, (hipStream_t)stream);   // (no launch for n_samples == 0)
     HIPCHK(hipGetLastError());
     return FUIFGPU_OK;
 }

@@ -160,6 +160,19 @@ struct Plan {
     std::string message;
 };
 
+// One channel of the writer's forward Quantize on the GPU (transforms.hip k_fwd_quantize): n samples at `plane` (device) divided by q
+// in place, their range accumulated into pair `slot` of the launch's {min, max} array (slot < 0: no range).  first_block / n_blocks: the
+// channel's share of the launch's 1-D grid, filled in by fwd_quantize_channels_gpu
+struct QuantChan {
+    int32_t *plane;
+    int64_t n;
+    int32_t q, slot;
+    int32_t first_block, n_blocks;
+};
+// every channel of the table in one launch and the ranges back with one copy (capi.hip): minmax_host gets n_channels {min, max} pairs,
+// pair k for the entry whose slot is k; a pair no sample went into stays {INT32_MAX, INT32_MIN}
+int fwd_quantize_channels_gpu(const QuantChan *channels, int n_channels, int32_t *minmax_host);
+
 // One channel group of a stream: where its header starts and the first channel it codes (index.cpp)
 struct GroupEntry {
     uint32_t start;

@@ -37,5 +37,11 @@ void launch_plane_checksums(const int32_t *planes, int64_t elems, int64_t stride
 void launch_scale(int32_t *plane, int64_t n, int q, hipStream_t stream);   // transform/quantize.h:32-49 on one plane
 void launch_fwd_ycocg(int32_t *c0, int32_t *c1, int32_t *c2, int64_t n, hipStream_t stream);
 void launch_fwd_squeeze(bool horizontal, const int32_t *in, int w, int h, int32_t *avg, int32_t *res, hipStream_t stream);
+// forward Quantize (transform/quantize.h:54-71) with the range of the quotients: one plane, or every channel of a device table in one launch
+// (entry k owns blocks [first_block, first_block + n_blocks) of the grid, n_blocks = fwd_quantize_blocks(n), total_blocks their sum).
+// dev_minmax: {min, max} pairs the caller has initialised; NULL (one plane) = no range wanted
+int fwd_quantize_blocks(int64_t n_samples);
+void launch_fwd_quantize_plane(int32_t *plane, int64_t n, int q, int32_t *dev_minmax, hipStream_t stream);
+void launch_fwd_quantize(const QuantChan *dev_table, int n_channels, int total_blocks, int32_t *dev_minmax, hipStream_t stream);
 
 }  // namespace fuifgpu

@@ -976,8 +976,77 @@ void launch_scale(int32_t *plane, int64_t n, int q, hipStream_t stream) {
     if (n <= 0 || q == 1) return;
     hipLaunchKernelGGL(k_scale, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65535)), dim3(256), 0, stream, plane, n, q);
 }
+// transform/quantize.h:54-71 fwd_quantize of one plane, in place: every sample divided by the channel's constant, truncating toward
+// zero like C.  The range of the quotients (what encoding.cpp:737-739 recomputes before the stream is written) comes out of the same
+// pass: every lane keeps its own minimum and maximum over its grid-stride samples, the block folds the 256 pairs through LDS, and
+// ONE lane per block touches the two result words.  The division is the compiler's: q is uniform, the pass moves 8 bytes per sample.
+// (LDS, __syncthreads, atomicMax and atomicCAS are what the wavefront emulator of the CPU suite offers; no atomicMin, no shuffles.)
+__device__ __forceinline__ void atomic_min_i32(int32_t *p, int32_t v) {
+    int32_t seen = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    while (v < seen) {
+        const int32_t was = atomicCAS(p, seen, v);
+        if (was == seen) break;
+        seen = was;
+    }
+}
+__device__ __forceinline__ void fwd_quantize_plane(int32_t *plane, int64_t n, int q, int32_t *minmax, int block, int n_blocks) {
+    __shared__ int32_t s_mn[256], s_mx[256];
+    const int t = threadIdx.x;
+    if ((int64_t)block * 256 >= n) return;   // the whole block: it has no sample of this plane
+    int32_t mn = INT32_MAX, mx = INT32_MIN;
+    const int64_t first = (int64_t)block * 256 + t, step = (int64_t)n_blocks * 256;
+    // four samples per load and store where the plane starts on a 16-byte boundary (every plane of the writer does); the last n & 3
+    // samples, or a plane that does not, go one by one
+    const int64_t n4 = (reinterpret_cast<uintptr_t>(plane) & 15) == 0 ? n >> 2 : 0;
+    int4 *quads = reinterpret_cast<int4 *>(plane);
+    for (int64_t i = first; i < n4; i += step) {
+        int4 v = quads[i];
+        v.x /= q; v.y /= q; v.z /= q; v.w /= q;
+        if (q != 1) quads[i] = v;
+        mn = min(min(mn, v.x), min(min(v.y, v.z), v.w)); mx = max(max(mx, v.x), max(max(v.y, v.z), v.w));
+    }
+    for (int64_t i = 4 * n4 + first; i < n; i += step) {
+        const int32_t v = plane[i] / q;
+        if (q != 1) plane[i] = v;
+        mn = min(mn, v); mx = max(mx, v);
+    }
+    if (!minmax) return;
+    s_mn[t] = mn; s_mx[t] = mx;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) { s_mn[t] = min(s_mn[t], s_mn[t + s]); s_mx[t] = max(s_mx[t], s_mx[t + s]); }
+        __syncthreads();
+    }
+    if (t == 0) { atomic_min_i32(minmax, s_mn[0]); atomicMax(minmax + 1, s_mx[0]); }
+}
+// every channel of a picture in one launch: the channels' blocks lie one behind the other in a 1-D grid (QuantChan::first_block, n_blocks),
+// so a picture's 60 channels of very different sizes cost no empty blocks; a block finds its channel by bisection (uniform: scalar loads).
+// minmax + 2 * slot is the channel's {min, max} pair
+__global__ __launch_bounds__(256) void k_fwd_quantize(const QuantChan *table, int n_channels, int32_t *minmax) {
+    const int b = blockIdx.x;
+    int lo = 0, hi = n_channels - 1;       // the last entry whose first_block <= b (entries without blocks share their successor's)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].first_block <= b) lo = mid; else hi = mid - 1;
+    }
+    const QuantChan c = table[lo];
+    fwd_quantize_plane(c.plane, c.n, c.q, c.slot >= 0 ? minmax + 2 * (int64_t)c.slot : nullptr, b - c.first_block, c.n_blocks);
+}
+__global__ __launch_bounds__(256) void k_fwd_quantize_plane(int32_t *plane, int64_t n, int q, int32_t *minmax) {
+    fwd_quantize_plane(plane, n, q, minmax, blockIdx.x, gridDim.x);
+}
+// blocks per plane: 2048 samples (two loads of four per lane) each until the grid is wide enough to fill the device
+int fwd_quantize_blocks(int64_t n) { return n <= 0 ? 0 : (int)std::min<int64_t>((n + 2047) / 2048, 1024); }
+void launch_fwd_quantize(const QuantChan *dev_table, int n_channels, int total_blocks, int32_t *dev_minmax, hipStream_t stream) {
+    if (n_channels <= 0 || total_blocks <= 0) return;
+    hipLaunchKernelGGL(k_fwd_quantize, dim3((unsigned)total_blocks), dim3(256), 0, stream, dev_table, n_channels, dev_minmax);
+}
+void launch_fwd_quantize_plane(int32_t *plane, int64_t n, int q, int32_t *dev_minmax, hipStream_t stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_fwd_quantize_plane, dim3((unsigned)fwd_quantize_blocks(n)), dim3(256), 0, stream, plane, n, q, dev_minmax);
+}
 void launch_fwd_ycocg(int32_t *c0, int32_t *c1, int32_t *c2, int64_t n, hipStream_t stream) {
-    hipLaunchKernelGGL(k_fwd_ycocg, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, c0, c1, c2, n);
+    hipLaunchKernelGGL(k_fwd_ycocg,dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, c0, c1, c2, n);
 }
 void launch_fwd_squeeze(bool horizontal, const int32_t *in, int w, int h, int32_t *avg, int32_t *res, hipStream_t stream) {
     if (horizontal) hipLaunchKernelGGL(k_fwd_hsqueeze, dim3(((w + 1) / 2 + 255) / 256, h), dim3(256), 0, stream, in, w, h, avg, res);

@@ -281,6 +281,12 @@ int fuifgpu_fwd_ycocg(int32_t *c0, int32_t *c1, int32_t *c2, int w, int h, void 
 int fuifgpu_fwd_hsqueeze(const int32_t *in, int w, int h, int32_t *avg, int32_t *res, void *stream);
 /* transform/squeeze.h:227-263 fwd_vsqueeze: in w x h -> avg w x ((h+1)/2) + residual w x (h/2) */
 int fuifgpu_fwd_vsqueeze(const int32_t *in, int w, int h, int32_t *avg, int32_t *res, void *stream);
+/* transform/quantize.h:54-71 fwd_quantize of one plane, in place: plane[i] = plane[i] / q, truncating toward zero (samples are int16 values
+ * widened, as for the other forward entry points).  minmax_device != NULL: the minimum and the maximum of the quotients are accumulated
+ * into minmax_device[0] and [1] (device memory, which the caller initialises, e.g. to INT32_MAX / INT32_MIN) -- the ranges
+ * encoding/encoding.cpp:737-739 recomputes before a stream is written.  n_samples == 0 touches nothing.  q < 1: FUIFGPU_E_ARG; q == 1 leaves
+ * the samples and still gives their range. */
+int fuifgpu_fwd_quantize(int32_t *plane, int64_t n_samples, int q, int32_t *minmax_device, void *stream);
 
 /* ---- stream writer (host C++; the input generator) --------------------
  * Writes a lossless FUIF stream the reference decoder accepts, with the format decisions of the
@@ -320,6 +326,33 @@ int fuifgpu_encode_image(const int32_t *planes, int w, int h, int nch, int bit_d
  * Replaces N runs of the reference's `fuif_encode_file` (encoding/encoding.cpp:727-735). */
 int fuifgpu_encode_images(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
                           uint8_t **blobs_out, size_t *sizes_out);
+/* ---- lossy streams: what `fuif -Q quality[,chroma_quality]` writes for PNM input (fuif.cpp:459-503, the Squeeze branch) ----
+ * After YCoCg and Squeeze every channel is divided by a constant that follows from the two qualities, the channel's number of pixel
+ * halvings (hcshift + vcshift) and one of two tables (fuif.cpp:70-76): the chroma table for components 1 and 2 whenever opt->ycocg is
+ * set (also for pictures of fewer than three channels, like the CLI), the luma table for everything else.  The transform list gets a
+ * Quantize entry without parameters; the constants travel in the channel headers (encoding/encoding.cpp:490, transform/quantize.h:54-71).
+ * With opt->squeeze == 0 the qualities are first remapped to (400 + x) / 5 (fuif.cpp:461-465: colour quantisation only).
+ * With tree_mode 0 the bytes are those of `fuif -I 0 -K 0 -X 0 -Y 0 -Q ...`.  With opt->gpu_forward the division and the ranges of the
+ * quotients run on the GPU too (fuifgpu_fwd_quantize's kernel, one launch per picture), and channels that quantise to all zero -- at the
+ * usual qualities the two finest chroma layers, fuif.cpp:75 -- are not copied back at all.
+ * The DCT route of the CLI (`-J`) is not offered here: see fuif_amd/jpeglike.py for DCT streams. */
+typedef struct {
+    uint32_t struct_size;   /* = sizeof(fuifgpu_lossy_options) of the CALLER's header, versioned like fuifgpu_encode_options: 0 or a size
+                               that is not a multiple of 4 is FUIFGPU_E_ARG; a struct that ends before chroma_quality means "same as quality" */
+    float quality;          /* -Q's first number, 0..100; NaN or anything outside is FUIFGPU_E_ARG */
+    float chroma_quality;   /* -Q's second number, 0..100, or anything above 100 = same as quality (the CLI's default, 101); NaN or negative
+                               is FUIFGPU_E_ARG */
+} fuifgpu_lossy_options;
+/* fuifgpu_encode_image / fuifgpu_encode_images with the quantisation step.  lossy == NULL, or both qualities >= 100 (fuif.cpp:459), writes
+ * exactly the bytes of the lossless call.  Found by symbol lookup: the ABI version does not change. */
+int fuifgpu_encode_image_lossy(const int32_t *planes, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
+                               const fuifgpu_lossy_options *lossy, uint8_t **blob_out, size_t *size_out);
+int fuifgpu_encode_images_lossy(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
+                                const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out);
+/* host: the constant fuif.cpp:459-503 gives one channel -- squeeze_option = opt->squeeze (the OPTION, not whether the picture was large
+ * enough to be squeezed), chroma_table = 1 for the chroma table, shift = hcshift + vcshift (capped at 15).  1 when both qualities are
+ * >= 100.  A negative shift or a quality the entry points above refuse gives -FUIFGPU_E_ARG. */
+int fuifgpu_quantization_constant(float quality, float chroma_quality, int squeeze_option, int chroma_table, int shift);
 /* channels already in a transform domain (e.g. the quantised DCT coefficient planes import/read_jpeg.h:56-184
  * builds): geometry + q + samples per channel, `transforms` = flat words {id, nparams, params...} of the
  * transforms that produced them; opt->squeeze adds the default Squeeze of the first nb_channels channels */
