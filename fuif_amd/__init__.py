@@ -120,6 +120,7 @@ ABI_SYMBOLS = [
     "fuifgpu_plan_packed_bytes", "fuifgpu_batch_pack_out", "fuifgpu_batch_download_packed",
     "fuifgpu_dev_alloc", "fuifgpu_dev_free", "fuifgpu_dev_upload", "fuifgpu_dev_download",
     "fuifgpu_encode_image_lossy", "fuifgpu_encode_images_lossy", "fuifgpu_quantization_constant",
+    "fuifgpu_encode_images_device", "fuifgpu_channel_stats", "fuifgpu_encode_plane_traffic",
     "fuifgpu_plane_checksums", "fuifgpu_device_count", "fuifgpu_set_device", "fuifgpu_get_device", "fuifgpu_batch_device", "fuifgpu_peer_copy", "fuifgpu_batch_set_in_flight",
 ]
 
@@ -220,6 +221,9 @@ def lib():
     L.fuifgpu_fwd_quantize.argtypes = [vp, C.c_int64, C.c_int, vp, vp]
     L.fuifgpu_encode_image_lossy.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.fuifgpu_encode_images_lossy.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.fuifgpu_encode_images_device.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.fuifgpu_channel_stats.argtypes = [vp, C.c_int64, vp, vp]
+    L.fuifgpu_encode_plane_traffic.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.fuifgpu_quantization_constant.argtypes = [C.c_float, C.c_float, C.c_int, C.c_int, C.c_int]
     L.fuifgpu_encode_image.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.fuifgpu_encode_images.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
@@ -536,6 +540,50 @@ def encode_images(images, bit_depth=8, ycocg=True, squeeze=True, max_properties=
         blobs.append(C.string_at(outs[k], sizes[k]))
         lib().fuifgpu_free_blob(C.c_void_p(outs[k]))
     return blobs
+
+
+def encode_images_device(planes, w=None, h=None, nch=None, bit_depth=8, ycocg=True, squeeze=True, max_properties=12, tree_mode=1, max_tree_nodes=4095,
+                         index=False, split_bits=None, quality=None, chroma_quality=None):
+    """pictures that already live in DEVICE memory -> list of .fuif byte strings, the bytes encode_images writes for the same samples
+    (fuifgpu_encode_images_device: the planes are read, never written, and no channel crosses to the host unless its group is rolled
+    back to "uncompressed").  planes: a list of integer device pointers (each nch planes of w*h int32; w, h, nch given), or an object
+    with data_ptr(), shape == (N, C, H, W), an int32 dtype and contiguous layout -- e.g. a torch tensor on the current device."""
+    split_bits = DEFAULT_SPLIT_BITS if split_bits is None else split_bits
+    if hasattr(planes, "data_ptr"):
+        shape = tuple(int(v) for v in planes.shape)
+        if len(shape) != 4 or "int32" not in str(planes.dtype) or (hasattr(planes, "is_contiguous") and not planes.is_contiguous()):
+            raise FuifGpuError(4, "encode_images_device: a tensor must be contiguous int32 of shape (N, C, H, W)")
+        n, nch, h, w = shape
+        ptrs = [planes.data_ptr() + 4 * k * nch * h * w for k in range(n)]
+    else:
+        ptrs = [int(p) if p else 0 for p in planes]
+        if w is None or h is None or nch is None:
+            raise FuifGpuError(4, "encode_images_device: w, h and nch go with a list of device pointers")
+    n = len(ptrs)
+    opt = make_encode_options(int(ycocg), int(squeeze), max_properties, tree_mode, max_tree_nodes, int(index), int(split_bits), 1, 1)
+    lossy = None if quality is None and chroma_quality is None else C.byref(make_lossy_options(quality, chroma_quality))
+    arr = (C.c_void_p * max(n, 1))(*ptrs)
+    outs = (C.c_void_p * max(n, 1))()
+    sizes = (C.c_size_t * max(n, 1))()
+    _check(lib().fuifgpu_encode_images_device(arr, n, int(w), int(h), int(nch), bit_depth, C.byref(opt), lossy, outs, sizes))
+    blobs = []
+    for k in range(n):
+        blobs.append(C.string_at(outs[k], sizes[k]))
+        lib().fuifgpu_free_blob(C.c_void_p(outs[k]))
+    return blobs
+
+
+def channel_stats(plane_device_ptr, n_samples, stats_device_ptr, stream=None):
+    """fuifgpu_channel_stats: {min, max, zero samples} of n int32 samples in DEVICE memory accumulated into three int32 of device
+    memory the caller has preset; asynchronous on `stream`"""
+    _check(lib().fuifgpu_channel_stats(plane_device_ptr, int(n_samples), stats_device_ptr, stream))
+
+
+def encode_plane_traffic():
+    """(host->device, device->host) bytes of whole planes / channels the last encode call of this thread moved (fuifgpu_encode_plane_traffic)"""
+    a, b = C.c_uint64(0), C.c_uint64(0)
+    _check(lib().fuifgpu_encode_plane_traffic(C.byref(a), C.byref(b)))
+    return int(a.value), int(b.value)
 
 
 def quantization_constant(quality, chroma_quality=None, squeeze=True, chroma_table=False, shift=0):

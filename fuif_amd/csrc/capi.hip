@@ -162,6 +162,41 @@ int fwd_quantize_channels_gpu(const QuantChan *channels, int n_channels, int32_t
     if (e != hipSuccess) return hip_fail(e, "fwd_quantize_channels_gpu");
     return FUIFGPU_OK;
 }
+
+// The writer's statistics of every device-resident channel of a batch: the triples and behind them the record table in ONE device buffer,
+// like fwd_quantize_channels_gpu -- one upload, one launch, one copy back.
+int channel_stats_gpu(const StatsRec *recs, int n_recs, int32_t *stats_host) {
+    if (n_recs <= 0) return FUIFGPU_OK;
+    const size_t triples = ((size_t)n_recs * 3 * sizeof(int32_t) + 15) / 16 * 16;
+    std::vector<uint8_t> host(triples + sizeof(StatsRec) * (size_t)n_recs);
+    int32_t *st = reinterpret_cast<int32_t *>(host.data());
+    StatsRec *table = reinterpret_cast<StatsRec *>(host.data() + triples);
+    int64_t total_blocks = 0;
+    for (int k = 0; k < n_recs; k++) {
+        st[3 * k] = INT32_MAX; st[3 * k + 1] = INT32_MIN + 1; st[3 * k + 2] = 0;
+        if (recs[k].n < 0 || recs[k].n > INT32_MAX || (!recs[k].plane && recs[k].n > 0)) return FUIFGPU_E_ARG;
+        table[k] = recs[k];
+        table[k].first_block = (int32_t)total_blocks;
+        table[k].n_blocks = channel_stats_blocks(recs[k].n);
+        total_blocks += table[k].n_blocks;
+    }
+    if (total_blocks > INT32_MAX) return FUIFGPU_E_ARG;
+    uint8_t *dev = nullptr;
+    HIPCHK(hipMalloc((void **)&dev, host.size()));
+    hipError_t e = hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_channel_stats(reinterpret_cast<const StatsRec *>(dev + triples), n_recs, StatsRec{}, (int)total_blocks, reinterpret_cast<int32_t *>(dev), nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(stats_host, dev, sizeof(int32_t) * 3 * (size_t)n_recs, hipMemcpyDeviceToHost);   // waits for the kernel
+    hipFree(dev);
+    if (e != hipSuccess) return hip_fail(e, "channel_stats_gpu");
+    return FUIFGPU_OK;
+}
+int dev_copy(void *dst_device, const void *src_device, size_t bytes) {
+    if (bytes) HIPCHK(hipMemcpy(dst_device, src_device, bytes, hipMemcpyDeviceToDevice));
+    return FUIFGPU_OK;
+}
 }  // namespace fuifgpu
 
 extern "C" {
@@ -1078,6 +1113,13 @@ int fuifgpu_fwd_vsqueeze(const int32_t *in, int w, int h, int32_t *avg, int32_t 
 int fuifgpu_fwd_quantize(int32_t *plane, int64_t n_samples, int q, int32_t *minmax_device, void *stream) {
     if (q < 1 || n_samples < 0 || (!plane && n_samples > 0)) return FUIFGPU_E_ARG;
     launch_fwd_quantize_plane(plane, n_samples, q, minmax_device, (hipStream_t)stream);   // (no launch for n_samples == 0)
+    HIPCHK(hipGetLastError());
+    return FUIFGPU_OK;
+}
+int fuifgpu_channel_stats(const int32_t *plane_device, int64_t n_samples, int32_t *stats3_device, void *stream) {
+    if (n_samples < 0 || n_samples > INT32_MAX || ((!plane_device || !stats3_device) && n_samples > 0)) return FUIFGPU_E_ARG;   // (the zero count is an int32)
+    const int blocks = channel_stats_blocks(n_samples);
+    launch_channel_stats(nullptr, 1, StatsRec{plane_device, n_samples, 0, blocks}, blocks, stats3_device, (hipStream_t)stream);   // (no launch for n_samples == 0)
     HIPCHK(hipGetLastError());
     return FUIFGPU_OK;
 }

@@ -173,6 +173,20 @@ struct QuantChan {
 // pair k for the entry whose slot is k; a pair no sample went into stays {INT32_MAX, INT32_MIN}
 int fwd_quantize_channels_gpu(const QuantChan *channels, int n_channels, int32_t *minmax_host);
 
+// One plane of the writer's statistics launch (transforms.hip k_channel_stats): n samples at `plane` (device), read only; record k of a
+// launch accumulates {min, max, number of zero samples} into stats[3k .. 3k+2].  first_block / n_blocks: the record's share of the launch's
+// 1-D grid, filled in by channel_stats_gpu
+struct StatsRec {
+    const int32_t *plane;
+    int64_t n;
+    int32_t first_block, n_blocks;
+};
+// every record in one launch and the triples back with one copy (capi.hip): stats_host gets n_recs triples, each preset to what
+// Chan::minmax gives an empty channel ({INT32_MAX, INT32_MIN + 1, 0})
+int channel_stats_gpu(const StatsRec *recs, int n_recs, int32_t *stats_host);
+// device -> device copy on the null stream (the writer's working copies of caller-owned planes)
+int dev_copy(void *dst_device, const void *src_device, size_t bytes);
+
 // One channel group of a stream: where its header starts and the first channel it codes (index.cpp)
 struct GroupEntry {
     uint32_t start;

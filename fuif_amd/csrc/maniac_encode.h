@@ -51,6 +51,29 @@ struct EncJob {            // host side of one job
 // Runs every job's context model (one launch, blockIdx.y = job) and then every job's coder (one wavefront per job).
 int maniac_encode_jobs_gpu(std::vector<EncJob> &jobs, const uint16_t *pixel_table);
 
+// ---- the tree learner's samples of many groups in one launch ----------------------------------------------------------------
+struct LearnJobDev {       // what k_learn_samples_jobs sees of one job; all pointers are device pointers
+    EncGroup g;
+    int64_t n_samples, stride;   // sample s is pixel s * stride (row-major)
+    int32_t nprops, pad;         // 2 * g.nrefs + 13
+    int32_t *props;              // n_samples rows of nprops properties
+    uint8_t *bucket;             // n_samples residual classes: 0 for a zero residual d, else ilog2(|d|) + 1
+};
+struct LearnJob {          // host side of one job
+    EncGroup g;                  // device pointers of the planes
+    int64_t n_samples = 0, stride = 1;
+    int nprops = 0;
+};
+struct LearnSamples {      // every job's rows and buckets, as they came back in one copy
+    std::vector<int32_t> raw;    // n_words property words, then the bucket bytes
+    size_t n_words = 0;
+    std::vector<size_t> props_off, bucket_off;   // per job: first word / first byte
+    const int32_t *props(size_t job) const { return raw.data() + props_off[job]; }
+    const uint8_t *bucket(size_t job) const { return reinterpret_cast<const uint8_t *>(raw.data() + n_words) + bucket_off[job]; }
+};
+// Computes what the host learner's sampling loop computes (writer.cpp encode_group) for every job, in its order.
+int learn_samples_jobs_gpu(const std::vector<LearnJob> &jobs, LearnSamples &out);
+
 // grow-only device buffers of one encode call
 struct EncScratch {
     int32_t *d_guess = nullptr, *d_leaf = nullptr;

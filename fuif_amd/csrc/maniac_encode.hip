@@ -24,6 +24,11 @@
 // dependent read and a write per binary decision, by lane 0); the batch coder (enc_rac_run_wave) runs the scalar code on the whole
 // wavefront and keeps the current leaf in a register with the next one prefetched, as the decoder does.  Its 16 KB chance table in
 // LDS limits a CU to 9 such wavefronts: the first thing to look at once it can be timed.
+//
+//   k_learn_samples_jobs  one lane per SAMPLE of the host's tree learner: the properties and the residual class of every stride-th pixel of
+//                every group of a picture whose channels live only on the device (fuifgpu_encode_images_device) -- the same property code as
+//                k_enc_model (enc_props_and_guess), so the learner sees what the coder will see.  The batch path's first wall times, with and
+//                without the planes crossing PCIe, are in profiles/device_resident_encode.txt.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -58,12 +63,11 @@ DEV int e_median3(int a, int b, int c) {
 // ---------------------------------------------------------------------------------------------
 // context model of every pixel, in parallel
 namespace {
-DEV void enc_model_pixel(const EncGroup &g, const EncNode *tree, int n_nodes, int64_t i, int32_t *guess_out, int32_t *leaf_out) {
-    const int64_t n = (int64_t)g.w * g.h;
-    if (i >= n) return;
+// the 2k+13 properties of pixel i = (x, y) of a group into p[] (context_predict.h:124-168, 233-289, one pixel); returns its prediction.
+// The ONE copy of the property arithmetic on the device: the coder's context model and the learner's samples both come through here.
+DEV int enc_props_and_guess(const EncGroup &g, int64_t i, int32_t *p) {
     const int w = g.w;
     const int y = (int)(i / w), x = (int)(i - (int64_t)y * w);
-    int32_t p[kMaxProps];
     int o = 0;
     for (int k = 0; k < g.nrefs; k++) {   // context_predict.h:233-289, one pixel
         const EncRef rc = g.refs[k];
@@ -85,16 +89,21 @@ DEV void enc_model_pixel(const EncGroup &g, const EncNode *tree, int n_nodes, in
     p[o++] = left + top - topleft; p[o++] = topleft + topright - top;
     p[o++] = e_slog(left - topleft); p[o++] = e_slog(topleft - top); p[o++] = e_slog(top - topright);
     p[o++] = e_slog(top - toptop); p[o++] = e_slog(left - leftleft);
-    int guess;
     switch (g.predictor) {   // context_predict.h:157-166
-        case 0: guess = g.zero; break;
-        case 1: guess = (left + top) / 2; break;
-        case 3: guess = left; break;
-        case 4: guess = top; break;
-        case 5: guess = (left + topleft + top + topright) / 4; break;
-        case 6: { const int t = left + top - topleft; guess = t < g.minval ? g.minval : (t > g.maxval ? g.maxval : t); break; }
-        default: guess = e_median3(left + top - topleft, left, top); break;
+        case 0: return g.zero;
+        case 1: return (left + top) / 2;
+        case 3: return left;
+        case 4: return top;
+        case 5: return (left + topleft + top + topright) / 4;
+        case 6: { const int t = left + top - topleft; return t < g.minval ? g.minval : (t > g.maxval ? g.maxval : t); }
+        default: return e_median3(left + top - topleft, left, top);
     }
+}
+DEV void enc_model_pixel(const EncGroup &g, const EncNode *tree, int n_nodes, int64_t i, int32_t *guess_out, int32_t *leaf_out) {
+    const int64_t n = (int64_t)g.w * g.h;
+    if (i >= n) return;
+    int32_t p[kMaxProps];
+    const int guess = enc_props_and_guess(g, i, p);
     int pos = 0;
     EncNode nd = tree[0];
     for (int depth = 0; depth < n_nodes && nd.prop >= 0; depth++) {   // compound.h:142-153 (a walk visits every node at most once)
@@ -122,6 +131,24 @@ __global__ __launch_bounds__(256) void k_enc_model_jobs(const EncJobDev *jobs, c
     }
     const EncJobDev &j = jobs[lo];
     enc_model_pixel(j.g, j.tree, j.n_nodes, (int64_t)(blk - first_block[lo]) * 256 + threadIdx.x, j.guess, j.leaf);
+}
+
+// what the writer's tree learner looks at (csrc/writer.cpp, Learner): every stride-th pixel of a group, its properties and the zero/exponent
+// class of its residual.  One lane per sample, the jobs' blocks numbered through like k_enc_model_jobs'; a lane writes its own row of
+// nprops words (rows lie back to back: a wavefront's 64 rows are one contiguous run) and one bucket byte.
+__global__ __launch_bounds__(256) void k_learn_samples_jobs(const LearnJobDev *jobs, const uint32_t *first_block, int n_jobs) {
+    const uint32_t blk = blockIdx.x;
+    int lo = 0, hi = n_jobs - 1;
+    while (lo < hi) {                       // the last job whose first block is <= blk
+        const int mid = (lo + hi + 1) >> 1;
+        if (first_block[mid] <= blk) lo = mid; else hi = mid - 1;
+    }
+    const LearnJobDev &j = jobs[lo];
+    const int64_t s = (int64_t)(blk - first_block[lo]) * 256 + threadIdx.x;
+    if (s >= j.n_samples) return;
+    const int64_t i = s * j.stride;         // < w * h: n_samples = ceil(w * h / stride)
+    const int d = j.g.plane[i] - enc_props_and_guess(j.g, i, j.props + s * j.nprops);
+    j.bucket[s] = (uint8_t)(d == 0 ? 0 : e_ilog2((uint32_t)e_iabs(d)) + 1);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -349,6 +376,58 @@ DEV void enc_rac_run_wave(const int32_t *plane, const int32_t *guess, const int3
 __global__ __launch_bounds__(64) void k_enc_rac_jobs(const EncJobDev *jobs, const uint16_t *table_g) {
     const EncJobDev &j = jobs[blockIdx.x];
     enc_rac_run_wave(j.g.plane, j.guess, j.leaf, j.n, j.g.minval, j.g.maxval, j.leaves, table_g, j.state, j.out, j.out_cap);
+}
+
+// ---------------------------------------------------------------------------------------------
+// One arena: [LearnJobDev x nj][first blocks][every job's property rows][every job's bucket bytes]; the head goes up in one copy, the rows
+// and buckets come back in one.
+int learn_samples_jobs_gpu(const std::vector<LearnJob> &jobs, LearnSamples &out) {
+    out = LearnSamples();
+    const size_t nj = jobs.size();
+    if (!nj) return FUIFGPU_OK;
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t off_first = up(sizeof(LearnJobDev) * nj), head = off_first + up(sizeof(uint32_t) * (nj + 1));
+    out.props_off.resize(nj); out.bucket_off.resize(nj);
+    size_t words = 0, bytes = 0;
+    uint64_t blocks = 0;
+    std::vector<uint8_t> host(head, 0);
+    LearnJobDev *h_jobs = reinterpret_cast<LearnJobDev *>(host.data());
+    uint32_t *first = reinterpret_cast<uint32_t *>(host.data() + off_first);
+    for (size_t k = 0; k < nj; k++) {
+        const LearnJob &j = jobs[k];
+        const int64_t npix = (int64_t)j.g.w * j.g.h;
+        if (!j.g.plane || j.g.w < 1 || j.g.h < 1 || j.g.nrefs < 0 || j.g.nrefs > kMaxRefs || j.nprops != 2 * j.g.nrefs + kNonRefProps || j.stride < 1 ||
+            j.n_samples != (npix + j.stride - 1) / j.stride)
+            return FUIFGPU_E_ARG;
+        out.props_off[k] = words; words += (size_t)j.n_samples * (size_t)j.nprops;
+        out.bucket_off[k] = bytes; bytes += (size_t)j.n_samples;
+        first[k] = (uint32_t)blocks; blocks += ((uint64_t)j.n_samples + 255) / 256;
+    }
+    first[nj] = (uint32_t)blocks;
+    if (blocks > 0x7FFFFFFFull) return FUIFGPU_E_ARG;
+    const size_t result = words * sizeof(int32_t) + bytes;
+    uint8_t *arena = nullptr;
+    if (hipMalloc((void **)&arena, head + result) != hipSuccess) return FUIFGPU_E_HIP;
+    for (size_t k = 0; k < nj; k++) {
+        LearnJobDev &d = h_jobs[k];
+        d.g = jobs[k].g; d.n_samples = jobs[k].n_samples; d.stride = jobs[k].stride; d.nprops = jobs[k].nprops; d.pad = 0;
+        d.props = reinterpret_cast<int32_t *>(arena + head) + out.props_off[k];
+        d.bucket = arena + head + words * sizeof(int32_t) + out.bucket_off[k];
+    }
+    int rc = FUIFGPU_OK;
+#define ECHK(call) do { if (rc == FUIFGPU_OK && (call) != hipSuccess) rc = FUIFGPU_E_HIP; } while (0)
+    ECHK(hipMemcpy(arena, host.data(), head, hipMemcpyHostToDevice));
+    if (rc == FUIFGPU_OK) {
+        hipLaunchKernelGGL(k_learn_samples_jobs, dim3((unsigned)blocks), dim3(256), 0, nullptr, reinterpret_cast<const LearnJobDev *>(arena),
+                           reinterpret_cast<const uint32_t *>(arena + off_first), (int)nj);
+        ECHK(hipGetLastError());
+    }
+    out.raw.resize((result + 3) / 4);
+    out.n_words = words;
+    ECHK(hipMemcpy(out.raw.data(), arena + head, result, hipMemcpyDeviceToHost));   // synchronises with the null stream's kernels
+#undef ECHK
+    hipFree(arena);
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -43,5 +43,10 @@ void launch_fwd_squeeze(bool horizontal, const int32_t *in, int w, int h, int32_
 int fwd_quantize_blocks(int64_t n_samples);
 void launch_fwd_quantize_plane(int32_t *plane, int64_t n, int q, int32_t *dev_minmax, hipStream_t stream);
 void launch_fwd_quantize(const QuantChan *dev_table, int n_channels, int total_blocks, int32_t *dev_minmax, hipStream_t stream);
+// {min, max, zero samples} of read-only planes, accumulated into caller-initialised triples: every record of a device table in one launch
+// (record k owns blocks [first_block, first_block + n_blocks), n_blocks = channel_stats_blocks(n), into dev_stats + 3k), or dev_table == NULL: the one
+// record `one` (first_block 0) into dev_stats
+int channel_stats_blocks(int64_t n_samples);
+void launch_channel_stats(const StatsRec *dev_table, int n_recs, StatsRec one, int total_blocks, int32_t *dev_stats, hipStream_t stream);
 
 }  // namespace fuifgpu

@@ -980,7 +980,8 @@ void launch_scale(int32_t *plane, int64_t n, int q, hipStream_t stream) {
 // zero like C.  The range of the quotients (what encoding.cpp:737-739 recomputes before the stream is written) comes out of the same
 // pass: every lane keeps its own minimum and maximum over its grid-stride samples, the block folds the 256 pairs through LDS, and
 // ONE lane per block touches the two result words.  The division is the compiler's: q is uniform, the pass moves 8 bytes per sample.
-// (LDS, __syncthreads, atomicMax and atomicCAS are what the wavefront emulator of the CPU suite offers; no atomicMin, no shuffles.)
+// (LDS, __syncthreads, atomicMax and atomicCAS are what the wavefront emulator of the CPU suite offered when this was written; it has
+// had atomicMin and __shfl_xor since k_channel_stats below.)
 __device__ __forceinline__ void atomic_min_i32(int32_t *p, int32_t v) {
     int32_t seen = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     while (v < seen) {
@@ -1044,6 +1045,52 @@ void launch_fwd_quantize(const QuantChan *dev_table, int n_channels, int total_b
 void launch_fwd_quantize_plane(int32_t *plane, int64_t n, int q, int32_t *dev_minmax, hipStream_t stream) {
     if (n <= 0) return;
     hipLaunchKernelGGL(k_fwd_quantize_plane, dim3((unsigned)fwd_quantize_blocks(n)), dim3(256), 0, stream, plane, n, q, dev_minmax);
+}
+// {min, max, zero samples} of planes nobody writes: what the writer needs of a transformed channel before it codes it (encoding.cpp:737-739
+// and the "predictability" byte of encoding.cpp:113-121) when the channel stays on the device.  One read per sample, nothing stored: up to three
+// samples one by one until the address is a multiple of 16, four per load from there, the last ones one by one again.  Every lane folds its
+// grid-stride samples, the wavefront folds its 64 lanes with shuffles, and ONE lane per wavefront touches the three result words.
+__global__ __launch_bounds__(256) void k_channel_stats(const StatsRec *table, int n_recs, StatsRec one, int32_t *stats) {
+    const int b = blockIdx.x;
+    int lo = 0;
+    if (table) {
+        int hi = n_recs - 1;                // the last record whose first_block <= b (records without blocks share their successor's)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (table[mid].first_block <= b) lo = mid; else hi = mid - 1;
+        }
+        one = table[lo];
+    }
+    const int64_t n = one.n;
+    const int64_t first = (int64_t)(b - one.first_block) * 256 + threadIdx.x, step = (int64_t)one.n_blocks * 256;
+    if (first - threadIdx.x >= n) return;   // the whole block: it has no sample of this plane
+    const int32_t *plane = one.plane;
+    const int64_t to16 = (int64_t)((4 - ((reinterpret_cast<uintptr_t>(plane) >> 2) & 3)) & 3), head = to16 < n ? to16 : n;
+    const int64_t n4 = (n - head) >> 2, ends = n - 4 * n4;   // ends: the samples in front of and behind the quads
+    const int4 *quads = reinterpret_cast<const int4 *>(plane + head);
+    int32_t mn = INT32_MAX, mx = INT32_MIN, zeros = 0;
+    for (int64_t i = first; i < n4; i += step) {
+        const int4 v = quads[i];
+        mn = min(min(mn, v.x), min(min(v.y, v.z), v.w)); mx = max(max(mx, v.x), max(max(v.y, v.z), v.w));
+        zeros += (v.x == 0) + (v.y == 0) + (v.z == 0) + (v.w == 0);
+    }
+    for (int64_t k = first; k < ends; k += step) {
+        const int32_t v = plane[k < head ? k : k + 4 * n4];
+        mn = min(mn, v); mx = max(mx, v); zeros += v == 0;
+    }
+    for (int m = 1; m < 64; m <<= 1) {
+        mn = min(mn, __shfl_xor(mn, m)); mx = max(mx, __shfl_xor(mx, m)); zeros += __shfl_xor(zeros, m);
+    }
+    if ((threadIdx.x & 63) == 0 && mn <= mx) {   // (a wavefront none of whose lanes had a sample keeps mn > mx)
+        int32_t *s = stats + 3 * (int64_t)lo;
+        atomicMin(s, mn); atomicMax(s + 1, mx); atomicAdd(s + 2, zeros);
+    }
+}
+// blocks per plane: 2048 samples (two loads of four per lane) each until the grid is wide enough to fill the device
+int channel_stats_blocks(int64_t n) { return fwd_quantize_blocks(n); }
+void launch_channel_stats(const StatsRec *dev_table, int n_recs, StatsRec one, int total_blocks, int32_t *dev_stats, hipStream_t stream) {
+    if (total_blocks <= 0) return;
+    hipLaunchKernelGGL(k_channel_stats, dim3((unsigned)total_blocks), dim3(256), 0, stream, dev_table, n_recs, one, dev_stats);
 }
 void launch_fwd_ycocg(int32_t *c0, int32_t *c1, int32_t *c2, int64_t n, hipStream_t stream) {
     hipLaunchKernelGGL(k_fwd_ycocg,dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, c0, c1, c2, n);

@@ -17,6 +17,8 @@
 // writer's OWN greedy top-down learner (bucket-entropy gain on sampled pixels), not the
 // reference's two-pass virtual-chance learner (maniac/compound_enc.h), so those files are valid
 // FUIF with realistic tree sizes but not byte-identical to the reference's.
+// fuifgpu_encode_images_device: the pictures are in device memory and the transformed channels stay there (Chan::resident); the host sees
+// three integers per channel (k_channel_stats) and the learner's samples (k_learn_samples_jobs), and writes the same bytes.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -50,6 +52,9 @@ struct Chan {
     int w = 0, h = 0, minval = 0, maxval = 0, zero = 0, q = 1;
     int hshift = 0, vshift = 0, hcshift = 0, vcshift = 0, component = -1;
     mutable int32_t *dev = nullptr;   // gpu_forward: the samples live here (w x h, contiguous) until every transform has run; gpu_entropy: a device copy of `data`
+    int64_t zeros = -1;               // number of zero samples when the statistics launch counted them (device-only channels), else -1
+    // device-only: `dev` is set and `data` is empty -- the samples never come to the host (fuifgpu_encode_images_device)
+    bool resident() const { return dev && data.empty(); }
     void setzero() { zero = minval > 0 ? minval : (maxval < 0 ? maxval : 0); }
     void minmax() {
         int mn = 0x7FFFFFFF, mx = (int)0x80000001;
@@ -520,14 +525,53 @@ struct GroupCoder {
     int gpu_entropy = 0;            // the pixel loop of compressed groups runs in maniac_encode.hip
     EncScratch *scratch = nullptr;  // its device buffers, reused from group to group
     int *gpu_rc = nullptr;          // first error of that path (there is no host route behind it)
+    // device-only channels: the learner's samples of the picture's groups as k_learn_samples_jobs computed them, sample_job[channel] = job or -1
+    const LearnSamples *samples = nullptr;
+    const std::vector<int> *sample_job = nullptr;
 };
+
+// bytes of whole planes / channels the current encode call of this thread has moved (fuifgpu_encode_plane_traffic): every copy of
+// channel samples between host and device goes through these two
+thread_local uint64_t g_plane_h2d = 0, g_plane_d2h = 0;
+int plane_upload(int32_t *dev, const int32_t *host, size_t samples) {
+    g_plane_h2d += sizeof(int32_t) * samples;
+    return fuifgpu_dev_upload(dev, host, sizeof(int32_t) * samples);
+}
+int plane_download(int32_t *host, const int32_t *dev, size_t samples) {
+    g_plane_d2h += sizeof(int32_t) * samples;
+    return fuifgpu_dev_download(host, dev, sizeof(int32_t) * samples);
+}
 
 // a device copy of a channel's samples for the GPU pixel loop (kept until the stream is written)
 int ensure_dev(const Chan &c) {
     if (c.dev || c.data.empty()) return FUIFGPU_OK;
     c.dev = (int32_t *)fuifgpu_dev_alloc(sizeof(int32_t) * c.data.size());
     if (!c.dev) return FUIFGPU_E_HIP;
-    return fuifgpu_dev_upload(c.dev, c.data.data(), sizeof(int32_t) * c.data.size());
+    return plane_upload(c.dev, c.data.data(), c.data.size());
+}
+
+// what the learner samples of a group (encode_group): every stride-th pixel, none for small groups or fixed trees
+struct LearnPlan {
+    size_t stride = 0, n_samples = 0;   // stride 0: no learned tree
+    int max_depth = 14, min_leaf = 48;
+};
+LearnPlan plan_learner(const Chan &c, int tree_mode, int max_tree_nodes) {
+    LearnPlan lp;
+    const size_t npix = (size_t)c.w * c.h;
+    if (tree_mode != 1 || npix < 4096) return lp;
+    // sample pixels on a coprime stride so every row/column phase is seen
+    size_t target = 60000;
+    if (max_tree_nodes > 4095) {
+        // a caller who lifts the node cap above the default wants trees of that size (the reference encoder's reach 19 000 nodes
+        // with `-I 16`; the format allows 65 535, compound.h:46): 60 000 samples in leaves of >= 48 stop near 2 500 nodes, so the
+        // sample, the depth and the smallest leaf scale with the cap.  The default cap keeps the default rule and its bytes.
+        target = (size_t)max_tree_nodes * 16;
+        lp.max_depth = 40; lp.min_leaf = 6;
+    }
+    lp.stride = std::max<size_t>(1, npix / target);
+    if (lp.stride > 1 && lp.stride % 2 == 0) lp.stride++;
+    lp.n_samples = (npix + lp.stride - 1) / lp.stride;
+    return lp;
 }
 
 // serialise a learned tree in pre-order (write side of compound.h:277-308) and build the
@@ -599,7 +643,8 @@ size_t encode_group(Bytes &io, Image &img, int ci, int predictor, bool compress,
     int predictability = 2048;
     if (predictor == 0 && compress) {
         uint64_t zeroes = 0, pixels = (uint64_t)c.w * c.h;
-        for (int32_t v : c.data) zeroes += (v == 0);
+        if (c.zeros >= 0) zeroes = (uint64_t)c.zeros;
+        else for (int32_t v : c.data) zeroes += (v == 0);
         int rounded = (int)(zeroes * 128 / pixels);
         rounded = std::max(1, std::min(127, rounded));
         io.varint((size_t)rounded);
@@ -607,7 +652,13 @@ size_t encode_group(Bytes &io, Image &img, int ci, int predictor, bool compress,
     }
     RacEnc rac(io);
     if (!compress) {
-        for (int32_t v : c.data) uniform_write(rac, c.minval, c.maxval - c.minval, v);
+        std::vector<int32_t> fetched;   // a device-only channel comes to the host for this one loop
+        if (c.resident()) {
+            fetched.resize((size_t)c.w * c.h);
+            const int rc = plane_download(fetched.data(), c.dev, fetched.size());
+            if (rc != FUIFGPU_OK && gc.gpu_rc && *gc.gpu_rc == FUIFGPU_OK) *gc.gpu_rc = rc;
+        }
+        for (int32_t v : c.resident() ? fetched : c.data) uniform_write(rac, c.minval, c.maxval - c.minval, v);
         rac.flush();
         return io.b.size() - header_pos;
     }
@@ -615,21 +666,20 @@ size_t encode_group(Bytes &io, Image &img, int ci, int predictor, bool compress,
     Learner L;
     const Learner *use = nullptr;
     const size_t npix = (size_t)c.w * c.h;
-    if (gc.tree_mode == 1 && npix >= 4096) {
-        // sample pixels on a coprime stride so every row/column phase is seen
-        size_t target = 60000;
-        if (gc.max_tree_nodes > 4095) {
-            // a caller who lifts the node cap above the default wants trees of that size (the reference encoder's reach 19 000 nodes
-            // with `-I 16`; the format allows 65 535, compound.h:46): 60 000 samples in leaves of >= 48 stop near 2 500 nodes, so the
-            // sample, the depth and the smallest leaf scale with the cap.  The default cap keeps the default rule and its bytes.
-            target = (size_t)gc.max_tree_nodes * 16;
-            L.max_depth = 40; L.min_leaf = 6;
-        }
-        size_t stride = std::max<size_t>(1, npix / target);
-        if (stride > 1 && stride % 2 == 0) stride++;
+    const LearnPlan lp = plan_learner(c, gc.tree_mode, gc.max_tree_nodes);
+    if (lp.stride) {
+        const size_t stride = lp.stride;
+        L.max_depth = lp.max_depth; L.min_leaf = lp.min_leaf;
         L.nprops = nprops; L.scale = (double)stride; L.max_nodes = gc.max_tree_nodes;
         L.threshold_bits = (double)gc.split_bits;
-        for (size_t i = 0; i < npix; i += stride) {
+        if (c.resident()) {   // the same rows, in the same order, from the device
+            const int job = gc.samples && gc.sample_job ? (*gc.sample_job)[(size_t)ci] : -1;
+            if (job < 0) { if (gc.gpu_rc && *gc.gpu_rc == FUIFGPU_OK) *gc.gpu_rc = FUIFGPU_E_HIP; }
+            else {
+                L.props.assign(gc.samples->props((size_t)job), gc.samples->props((size_t)job) + lp.n_samples * (size_t)nprops);
+                L.bucket.assign(gc.samples->bucket((size_t)job), gc.samples->bucket((size_t)job) + lp.n_samples);
+            }
+        } else for (size_t i = 0; i < npix; i += stride) {
             int y = (int)(i / c.w), x = (int)(i % c.w);
             int guess = props_and_guess(props.data(), c, refs, x, y, predictor);
             int d = c.data[i] - guess;
@@ -701,25 +751,28 @@ int write_stream(Image &img, int nch, int bit_depth, bool squeezed, const fuifgp
 }  // namespace fuifgpu
 
 // planes -> Image with the CLI's default forward transforms applied (fuif.cpp:380-455) and, with a quality, its Quantize (fuif.cpp:459-503),
-// on the host or on the GPU
+// on the host or on the GPU.  device_input: `planes` is device memory -- the forward transforms run on working copies there (gpu_forward is
+// implied) and the transformed channels STAY there, device-only (Chan::resident), for write_streams_batch
 static int build_transformed_image(const int32_t *planes, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options &o,
-                                   const fuifgpu::Lossy &lossy, fuifgpu::Image &img, bool &squeezed) {
+                                   const fuifgpu::Lossy &lossy, fuifgpu::Image &img, bool &squeezed, bool device_input = false) {
     using namespace fuifgpu;
     img.w = w; img.h = h; img.maxval = (1 << bit_depth) - 1; img.nb_channels = nch;
     img.ch.resize(nch);
     for (int c = 0; c < nch; c++) {
         Chan &ch = img.ch[c];
         ch.w = w; ch.h = h; ch.component = c; ch.minval = 0; ch.maxval = img.maxval;
-        ch.data.assign(planes + (size_t)c * w * h, planes + (size_t)(c + 1) * w * h);
+        if (!device_input) ch.data.assign(planes + (size_t)c * w * h, planes + (size_t)(c + 1) * w * h);
     }
-    const bool on_gpu = o.gpu_forward != 0;
+    const bool on_gpu = o.gpu_forward != 0 || device_input;
     int rc = FUIFGPU_OK;
     if (on_gpu) {
         // the planes go to the GPU once, every forward transform runs there, the transformed channels come back for the entropy coder
         for (int c = 0; c < nch && rc == FUIFGPU_OK; c++) {
             Chan &ch = img.ch[c];
             ch.dev = (int32_t *)fuifgpu_dev_alloc(sizeof(int32_t) * (size_t)w * h);
-            rc = ch.dev ? fuifgpu_dev_upload(ch.dev, ch.data.data(), sizeof(int32_t) * (size_t)w * h) : FUIFGPU_E_HIP;
+            if (!ch.dev) rc = FUIFGPU_E_HIP;
+            else if (device_input) rc = dev_copy(ch.dev, planes + (size_t)c * w * h, sizeof(int32_t) * (size_t)w * h);   // the caller's planes are never written
+            else rc = plane_upload(ch.dev, ch.data.data(), (size_t)w * h);
             ch.data.clear();
         }
     }
@@ -737,12 +790,12 @@ static int build_transformed_image(const int32_t *planes, int w, int h, int nch,
     }
     std::vector<char> all_zero(img.ch.size(), 0);   // gpu_forward + lossy: channels whose quotients are all 0 stay on the device
     if (rc == FUIFGPU_OK && lossy.active) rc = fwd_quantize(img, lossy, o.squeeze != 0, o.ycocg != 0, on_gpu, all_zero);   // fuif.cpp:459-503
-    if (on_gpu) {
+    if (on_gpu && (!device_input || rc != FUIFGPU_OK)) {
         for (size_t k = 0; k < img.ch.size(); k++) {
             Chan &ch = img.ch[k];
             if (rc == FUIFGPU_OK && ch.dev) {
                 ch.data.assign((size_t)ch.w * ch.h, 0);
-                if (!ch.data.empty() && !all_zero[k]) rc = fuifgpu_dev_download(ch.data.data(), ch.dev, sizeof(int32_t) * ch.data.size());
+                if (!ch.data.empty() && !all_zero[k]) rc = plane_download(ch.data.data(), ch.dev, ch.data.size());
             }
             if (ch.dev) fuifgpu_dev_free(ch.dev);
             ch.dev = nullptr;
@@ -778,6 +831,12 @@ static bool read_lossy_options(const fuifgpu_lossy_options *lossy, Lossy &l) {
     return read_qualities(lossy->quality, sz >= sizeof(fuifgpu_lossy_options) ? lossy->chroma_quality : 101.f, l);
 }
 
+int fuifgpu_encode_plane_traffic(uint64_t *h2d_bytes, uint64_t *d2h_bytes) {
+    if (h2d_bytes) *h2d_bytes = g_plane_h2d;
+    if (d2h_bytes) *d2h_bytes = g_plane_d2h;
+    return FUIFGPU_OK;
+}
+
 int fuifgpu_quantization_constant(float quality, float chroma_quality, int squeeze_option, int chroma_table, int shift) {
     Lossy l;
     if (shift < 0 || !read_qualities(quality, chroma_quality, l)) return -FUIFGPU_E_ARG;
@@ -795,6 +854,7 @@ int fuifgpu_encode_image_lossy(const int32_t *planes, int w, int h, int nch, int
     if (o.max_tree_nodes < 1) o.max_tree_nodes = 4095;
     if (o.max_tree_nodes > kMaxNodes) o.max_tree_nodes = kMaxNodes;
 
+    g_plane_h2d = g_plane_d2h = 0;
     Image img;
     bool squeezed = false;
     const int rc = build_transformed_image(planes, w, h, nch, bit_depth, o, l, img, squeezed);
@@ -822,6 +882,7 @@ int fuifgpu_encode_channels(const fuifgpu_raw_channel *channels, int n_channels,
     if (o.max_properties < 0 || o.max_properties > 2 * kMaxRefs) return FUIFGPU_E_ARG;
     if (o.max_tree_nodes < 1) o.max_tree_nodes = 4095;
     if (o.max_tree_nodes > kMaxNodes) o.max_tree_nodes = kMaxNodes;
+    g_plane_h2d = g_plane_d2h = 0;
     Image img;
     img.w = w; img.h = h; img.maxval = (1 << bit_depth) - 1; img.nb_channels = nb_channels;
     img.ch.resize(n_channels);
@@ -859,32 +920,60 @@ int fuifgpu_encode_channels(const fuifgpu_raw_channel *channels, int n_channels,
 namespace fuifgpu {
 namespace {
 
-int write_stream(Image &img, int nch, int bit_depth, bool squeezed, const fuifgpu_encode_options &o, uint8_t **blob_out, size_t *size_out,
-                 bool dct_style) {
-    const int w = img.w, h = img.h;
-    for (auto &c : img.ch) c.minmax();  // fuif_prepare_encode: encoding.cpp:737-743
+// ---- what write_stream and write_streams_batch share --------------------------------------------------------------------------------
+// fuif_prepare_encode (encoding.cpp:737-743): every channel's range from its samples.  Host channels are scanned here; device-only ones
+// (of all pictures) go through ONE k_channel_stats launch, which also counts their zeros for the "predictability" byte
+int channel_ranges(Image *imgs, size_t n_images) {
+    std::vector<StatsRec> recs;
+    std::vector<Chan *> who;
+    for (size_t m = 0; m < n_images; m++)
+        for (Chan &c : imgs[m].ch) {
+            if (!c.resident()) { c.minmax(); continue; }
+            recs.push_back(StatsRec{c.dev, (int64_t)c.w * c.h, 0, 0});
+            who.push_back(&c);
+        }
+    std::vector<int32_t> stats(3 * recs.size());
+    const int rc = channel_stats_gpu(recs.data(), (int)recs.size(), stats.data());
+    for (size_t k = 0; k < who.size() && rc == FUIFGPU_OK; k++) { who[k]->minval = stats[3 * k]; who[k]->maxval = stats[3 * k + 1]; who[k]->zeros = stats[3 * k + 2]; }
+    return rc;
+}
+int group_predictor(const Image &img, int i, bool squeezed, bool dct_style) {  // fuif.cpp:580-588
+    if (!squeezed && !dct_style) return 2;
+    return i < img.nb_meta + img.nb_channels ? 2 : 0;
+}
+void responsive_downscales(Image &img, bool squeezed, bool dct_style) {
     recompute_downscales(img);
     if (!squeezed && !dct_style) for (int s = 0; s < 6; s++) img.downscales[s] = (int)img.ch.size() - 1;
-
-    std::vector<uint16_t> tables(16384);
-    build_chance_table(tables.data(), 0xFFFFFFFFu / 19, 2);
-    build_chance_table(tables.data() + 8192, 0x0d000000u, 6);
-    GroupCoder gc{tables.data(), tables.data() + 8192, o.max_properties, o.tree_mode, o.max_tree_nodes, o.split_bits > 0 ? o.split_bits : 0};
-    EncScratch enc_scratch;
-    int gpu_rc = FUIFGPU_OK;
-    gc.gpu_entropy = o.gpu_entropy != 0; gc.scratch = &enc_scratch; gc.gpu_rc = &gpu_rc;
-    struct DevCleanup {   // device copies of the channels and the coder's buffers live as long as this call
-        Image &img; EncScratch &s;
-        ~DevCleanup() { for (Chan &c : img.ch) { if (c.dev) fuifgpu_dev_free(c.dev); c.dev = nullptr; } s.release(); }
-    } dev_cleanup{img, enc_scratch};
-
-    // encoding/encoding.cpp:455-573
-    Bytes head, io;
+}
+// the learner's samples of a picture's device-only groups (what encode_group's sampling loop computes for host channels), in one launch:
+// sample_job[channel] = its job in `out`, -1 for channels that learn nothing or have their samples on the host
+int learn_samples_device(Image &img, bool squeezed, const GroupCoder &gc, LearnSamples &out, std::vector<int> &sample_job) {
+    std::vector<LearnJob> jobs;
+    sample_job.assign(img.ch.size(), -1);
+    for (int i = 0; i < (int)img.ch.size(); i++) {
+        Chan &c = img.ch[i];
+        if (!c.resident() || !c.w || !c.h || c.minval == c.maxval) continue;
+        const LearnPlan lp = plan_learner(c, gc.tree_mode, gc.max_tree_nodes);
+        if (!lp.stride) continue;
+        c.setzero();
+        std::vector<Range> ranges; std::vector<RefInfo> refs;
+        LearnJob job;
+        job.nprops = init_properties(ranges, refs, img, i, i, gc.max_properties);
+        job.n_samples = (int64_t)lp.n_samples; job.stride = (int64_t)lp.stride;
+        const int rc = build_enc_group(c, refs, group_predictor(img, i, squeezed, false), job.g);
+        if (rc != FUIFGPU_OK) return rc;
+        sample_job[(size_t)i] = (int)jobs.size();
+        jobs.push_back(job);
+    }
+    return learn_samples_jobs_gpu(jobs, out);
+}
+// encoding/encoding.cpp:455-470: the fixed header fields into `head`, the transform list into `io`
+void begin_stream(const Image &img, int nch, int bit_depth, const fuifgpu_encode_options &o, Bytes &head, Bytes &io) {
     for (const char *m = "FUIF"; *m; m++) head.put(*m);
     head.varint((size_t)(nch + '0'));
     head.varint((size_t)(bit_depth + '&'));
-    head.varint((size_t)(w - 1));
-    head.varint((size_t)(h - 1));
+    head.varint((size_t)(img.w - 1));
+    head.varint((size_t)(img.h - 1));
     head.varint(0);  // colormodel
     head.varint((size_t)o.max_properties);
     io.varint(img.transforms.size());
@@ -892,32 +981,13 @@ int write_stream(Image &img, int nch, int bit_depth, bool squeezed, const fuifgp
         io.varint((size_t)((t.params.size() << 4) + t.id));
         for (int v : t.params) io.varint((size_t)v);
     }
-    int responsive[5] = {-1, -1, -1, -1, -1};
-    std::vector<GroupEntry> group_at;  // group starts relative to `io` (made absolute below)
-    const int n = (int)img.ch.size();
-    for (int i = 0; i < n; i++) {
-        Chan &c = img.ch[i];
-        if (!c.w || !c.h) continue;
-        int predictor = (i < img.nb_meta + img.nb_channels) ? 2 : 0;  // fuif.cpp:580-588
-        if (!squeezed && !dct_style) predictor = 2;
-        size_t header_pos = 0;
-        size_t before = io.b.size();
-        group_at.push_back(GroupEntry{(uint32_t)before, i});
-        size_t body = encode_group(io, img, i, predictor, true, gc, header_pos);
-        float bits = body * 8.0f, pixels = (float)c.w * c.h, ubits = 0.0f;
-        if (c.maxval > c.minval) ubits = pixels * (ilog2u((uint32_t)(c.maxval - c.minval)) + 1) + 16;
-        if (bits >= ubits && c.maxval > c.minval) {  // encoding.cpp:545-551: roll back, store uncompressed
-            io.b.resize(before);
-            encode_group(io, img, i, predictor, false, gc, header_pos);
-        } else if (bits >= ubits) {
-            // trivial channel: the reference re-encodes it "uncompressed" too (compress bit = 0)
-            io.b.resize(before);
-            encode_group(io, img, i, predictor, false, gc, header_pos);
-        }
-        size_t after = io.b.size();
-        for (int s = 0; s < 5; s++) if (img.downscales[s] >= i && img.downscales[s] <= i) responsive[s] = (int)after;
-    }
-    if (gpu_rc != FUIFGPU_OK) return gpu_rc;   // no host route behind the GPU pixel loop: the caller asked for it
+}
+// channel i's group ends at byte `after` of `io`
+void note_responsive(const Image &img, int i, size_t after, int responsive[5]) {
+    for (int s = 0; s < 5; s++) if (img.downscales[s] == i) responsive[s] = (int)after;
+}
+// encoding.cpp:552-573: the responsive offsets behind the header, the groups, the optional index trailer -> one malloc'ed blob
+int finish_stream(Bytes &head, const Bytes &io, int responsive[5], std::vector<GroupEntry> &group_at, bool emit_index, uint8_t **blob_out, size_t *size_out) {
     int rel = 0;
     for (int s = 0; s < 5; s++) {
         if (responsive[s] < 0) responsive[s] = (int)io.b.size();
@@ -925,12 +995,12 @@ int write_stream(Image &img, int nch, int bit_depth, bool squeezed, const fuifgp
         rel = responsive[s];
     }
     std::vector<uint8_t> trailer;
-    if (o.emit_index && !group_at.empty()) {
+    if (emit_index && !group_at.empty()) {
         // the transform list sits between the header and the first group: offsets become absolute here
         for (GroupEntry &g : group_at) g.start += (uint32_t)head.b.size();
         build_index_trailer(group_at, trailer);
     }
-    size_t total = head.b.size() + io.b.size() + trailer.size();
+    const size_t total = head.b.size() + io.b.size() + trailer.size();
     uint8_t *blob = (uint8_t *)malloc(total ? total : 1);
     if (!blob) return FUIFGPU_E_NOMEM;
     memcpy(blob, head.b.data(), head.b.size());
@@ -941,12 +1011,59 @@ int write_stream(Image &img, int nch, int bit_depth, bool squeezed, const fuifgp
     return FUIFGPU_OK;
 }
 
+int write_stream(Image &img, int nch, int bit_depth, bool squeezed, const fuifgpu_encode_options &o, uint8_t **blob_out, size_t *size_out,
+                 bool dct_style) {
+    EncScratch enc_scratch;
+    struct DevCleanup {   // device copies of the channels and the coder's buffers live as long as this call
+        Image &img; EncScratch &s;
+        ~DevCleanup() { for (Chan &c : img.ch) { if (c.dev) fuifgpu_dev_free(c.dev); c.dev = nullptr; } s.release(); }
+    } dev_cleanup{img, enc_scratch};
+    int gpu_rc = channel_ranges(&img, 1);
+    if (gpu_rc != FUIFGPU_OK) return gpu_rc;
+    responsive_downscales(img, squeezed, dct_style);
+
+    std::vector<uint16_t> tables(16384);
+    build_chance_table(tables.data(), 0xFFFFFFFFu / 19, 2);
+    build_chance_table(tables.data() + 8192, 0x0d000000u, 6);
+    GroupCoder gc{tables.data(), tables.data() + 8192, o.max_properties, o.tree_mode, o.max_tree_nodes, o.split_bits > 0 ? o.split_bits : 0};
+    gc.gpu_entropy = o.gpu_entropy != 0; gc.scratch = &enc_scratch; gc.gpu_rc = &gpu_rc;
+
+    // encoding/encoding.cpp:455-573
+    Bytes head, io;
+    begin_stream(img, nch, bit_depth, o, head, io);
+    int responsive[5] = {-1, -1, -1, -1, -1};
+    std::vector<GroupEntry> group_at;  // group starts relative to `io` (made absolute below)
+    const int n = (int)img.ch.size();
+    for (int i = 0; i < n; i++) {
+        Chan &c = img.ch[i];
+        if (!c.w || !c.h) continue;
+        const int predictor = group_predictor(img, i, squeezed, dct_style);
+        size_t header_pos = 0;
+        size_t before = io.b.size();
+        group_at.push_back(GroupEntry{(uint32_t)before, i});
+        size_t body = encode_group(io, img, i, predictor, true, gc, header_pos);
+        float bits = body * 8.0f, pixels = (float)c.w * c.h, ubits = 0.0f;
+        if (c.maxval > c.minval) ubits = pixels * (ilog2u((uint32_t)(c.maxval - c.minval)) + 1) + 16;
+        if (bits >= ubits) {
+            // encoding.cpp:545-551: roll back, store uncompressed; a trivial channel: the reference re-encodes it "uncompressed" too (compress bit = 0)
+            io.b.resize(before);
+            encode_group(io, img, i, predictor, false, gc, header_pos);
+        }
+        note_responsive(img, i, io.b.size(), responsive);
+    }
+    if (gpu_rc != FUIFGPU_OK) return gpu_rc;   // no host route behind the GPU pixel loop: the caller asked for it
+    return finish_stream(head, io, responsive, group_at, o.emit_index != 0, blob_out, size_out);
+}
+
 
 // ---- a batch of pictures: every compressed group's pixel loop in ONE launch pair ------------------------------------------------
 // Phase 1 (host, per picture): header fields, per group the header + zero chance + learned tree into its own byte buffer, the
 // coder's state behind the tree.  Phase 2 (GPU): maniac_encode_jobs_gpu -- the context model of every pixel of every group in
 // one launch, then one wavefront per group.  Phase 3 (host, per picture): flush, the roll-back to "uncompressed" of
 // encoding.cpp:545-551, responsive offsets, group index.  Same bytes as write_stream picture by picture.
+// Device-only channels (fuifgpu_encode_images_device) take the same three phases: their ranges and zero counts come from one
+// statistics launch, the learner's samples of a picture from one k_learn_samples_jobs launch, and build_enc_group hands their
+// buffers to the coder as they are; only a group that is rolled back comes to the host.
 struct PendingGroup {
     int channel = 0, predictor = 0, job = -1;   // job -1: a trivial channel (no coder)
     Bytes prefix;
@@ -954,30 +1071,33 @@ struct PendingGroup {
 };
 int write_streams_batch(std::vector<Image> &imgs, int nch, int bit_depth, const std::vector<char> &squeezed, const fuifgpu_encode_options &o,
                         uint8_t **blobs_out, size_t *sizes_out) {
-    std::vector<uint16_t> tables(16384);
-    build_chance_table(tables.data(), 0xFFFFFFFFu / 19, 2);
-    build_chance_table(tables.data() + 8192, 0x0d000000u, 6);
-    GroupCoder gc{tables.data(), tables.data() + 8192, o.max_properties, o.tree_mode, o.max_tree_nodes, o.split_bits > 0 ? o.split_bits : 0};
-    int gpu_rc = FUIFGPU_OK;
-    gc.gpu_rc = &gpu_rc;
     struct DevCleanup {
         std::vector<Image> &imgs;
         ~DevCleanup() { for (Image &im : imgs) for (Chan &c : im.ch) { if (c.dev) fuifgpu_dev_free(c.dev); c.dev = nullptr; } }
     } dev_cleanup{imgs};
+    std::vector<uint16_t> tables(16384);
+    build_chance_table(tables.data(), 0xFFFFFFFFu / 19, 2);
+    build_chance_table(tables.data() + 8192, 0x0d000000u, 6);
+    GroupCoder gc{tables.data(), tables.data() + 8192, o.max_properties, o.tree_mode, o.max_tree_nodes, o.split_bits > 0 ? o.split_bits : 0};
+    int gpu_rc = channel_ranges(imgs.data(), imgs.size());
+    if (gpu_rc != FUIFGPU_OK) return gpu_rc;
+    gc.gpu_rc = &gpu_rc;
     std::vector<EncJob> jobs;
     std::vector<std::vector<PendingGroup>> pending(imgs.size());
     for (size_t m = 0; m < imgs.size(); m++) {
         Image &img = imgs[m];
-        for (auto &c : img.ch) c.minmax();  // fuif_prepare_encode: encoding.cpp:737-743
-        recompute_downscales(img);
-        if (!squeezed[m]) for (int s = 0; s < 6; s++) img.downscales[s] = (int)img.ch.size() - 1;
+        responsive_downscales(img, squeezed[m] != 0, false);
+        LearnSamples samples;
+        std::vector<int> sample_job;
+        const int rc = learn_samples_device(img, squeezed[m] != 0, gc, samples, sample_job);
+        if (rc != FUIFGPU_OK) return rc;
+        gc.samples = &samples; gc.sample_job = &sample_job;
         for (int i = 0; i < (int)img.ch.size(); i++) {
             Chan &c = img.ch[i];
             if (!c.w || !c.h) continue;
             PendingGroup pg;
             pg.channel = i;
-            pg.predictor = (i < img.nb_meta + img.nb_channels) ? 2 : 0;  // fuif.cpp:580-588
-            if (!squeezed[m]) pg.predictor = 2;
+            pg.predictor = group_predictor(img, i, squeezed[m] != 0, false);
             if (c.minval != c.maxval) {
                 EncJob job;
                 encode_group(pg.prefix, img, i, pg.predictor, true, gc, pg.header_len, &job);
@@ -986,26 +1106,15 @@ int write_streams_batch(std::vector<Image> &imgs, int nch, int bit_depth, const 
             }
             pending[m].push_back(std::move(pg));
         }
+        gc.samples = nullptr; gc.sample_job = nullptr;
     }
     if (gpu_rc != FUIFGPU_OK) return gpu_rc;
     int rc = maniac_encode_jobs_gpu(jobs, gc.pixel_table);
     if (rc != FUIFGPU_OK) return rc;
     for (size_t m = 0; m < imgs.size(); m++) {
         Image &img = imgs[m];
-        const int w = img.w, h = img.h;
         Bytes head, io;
-        for (const char *mg = "FUIF"; *mg; mg++) head.put(*mg);
-        head.varint((size_t)(nch + '0'));
-        head.varint((size_t)(bit_depth + '&'));
-        head.varint((size_t)(w - 1));
-        head.varint((size_t)(h - 1));
-        head.varint(0);  // colormodel
-        head.varint((size_t)o.max_properties);
-        io.varint(img.transforms.size());
-        for (auto &t : img.transforms) {
-            io.varint((size_t)((t.params.size() << 4) + t.id));
-            for (int v : t.params) io.varint((size_t)v);
-        }
+        begin_stream(img, nch, bit_depth, o, head, io);
         int responsive[5] = {-1, -1, -1, -1, -1};
         std::vector<GroupEntry> group_at;
         for (PendingGroup &pg : pending[m]) {
@@ -1028,30 +1137,13 @@ int write_streams_batch(std::vector<Image> &imgs, int nch, int bit_depth, const 
             }
             if (uncompressed) {
                 size_t header_pos = 0;
-                encode_group(io, img, i, pg.predictor, false, gc, header_pos);
+                encode_group(io, img, i, pg.predictor, false, gc, header_pos);   // (a device-only channel comes to the host here)
             }
-            const size_t after = io.b.size();
-            for (int s = 0; s < 5; s++) if (img.downscales[s] >= i && img.downscales[s] <= i) responsive[s] = (int)after;
+            note_responsive(img, i, io.b.size(), responsive);
         }
-        int rel = 0;
-        for (int s = 0; s < 5; s++) {
-            if (responsive[s] < 0) responsive[s] = (int)io.b.size();
-            head.varint((size_t)(responsive[s] - rel));
-            rel = responsive[s];
-        }
-        std::vector<uint8_t> trailer;
-        if (o.emit_index && !group_at.empty()) {
-            for (GroupEntry &g : group_at) g.start += (uint32_t)head.b.size();
-            build_index_trailer(group_at, trailer);
-        }
-        const size_t total = head.b.size() + io.b.size() + trailer.size();
-        uint8_t *blob = (uint8_t *)malloc(total ? total : 1);
-        if (!blob) return FUIFGPU_E_NOMEM;
-        memcpy(blob, head.b.data(), head.b.size());
-        memcpy(blob + head.b.size(), io.b.data(), io.b.size());
-        if (!trailer.empty()) memcpy(blob + head.b.size() + io.b.size(), trailer.data(), trailer.size());
-        blobs_out[m] = blob;
-        sizes_out[m] = total;
+        if (gpu_rc != FUIFGPU_OK) return gpu_rc;
+        rc = finish_stream(head, io, responsive, group_at, o.emit_index != 0, &blobs_out[m], &sizes_out[m]);
+        if (rc != FUIFGPU_OK) return rc;
     }
     return FUIFGPU_OK;
 }
@@ -1059,8 +1151,9 @@ int write_streams_batch(std::vector<Image> &imgs, int nch, int bit_depth, const 
 }  // namespace
 }  // namespace fuifgpu
 
-extern "C" int fuifgpu_encode_images_lossy(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth,
-                                           const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out) {
+// the batch entry points: planes[m] on the host, or (device_input) in device memory
+static int encode_images_common(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
+                                const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out, bool device_input) {
     if (!planes || !blobs_out || !sizes_out || n_images < 1 || w < 1 || h < 1 || nch < 1 || nch > 8 || bit_depth < 1 || bit_depth > 14) return FUIFGPU_E_ARG;
     fuifgpu_encode_options o;
     Lossy l;
@@ -1068,20 +1161,34 @@ extern "C" int fuifgpu_encode_images_lossy(const int32_t *const *planes, int n_i
     if (o.max_properties < 0 || o.max_properties > 2 * kMaxRefs) return FUIFGPU_E_ARG;
     if (o.max_tree_nodes < 1) o.max_tree_nodes = 4095;
     if (o.max_tree_nodes > kMaxNodes) o.max_tree_nodes = kMaxNodes;
-    for (int m = 0; m < n_images; m++) { if (!planes[m]) return FUIFGPU_E_ARG; blobs_out[m] = nullptr; sizes_out[m] = 0; }
+    for (int m = 0; m < n_images; m++) { blobs_out[m] = nullptr; sizes_out[m] = 0; }
+    for (int m = 0; m < n_images; m++) if (!planes[m]) return FUIFGPU_E_ARG;
+    g_plane_h2d = g_plane_d2h = 0;
     std::vector<Image> imgs((size_t)n_images);
     std::vector<char> squeezed((size_t)n_images, 0);
-    for (int m = 0; m < n_images; m++) {
+    int rc = FUIFGPU_OK;
+    for (int m = 0; m < n_images && rc == FUIFGPU_OK; m++) {
         bool sq = false;
-        const int rc = build_transformed_image(planes[m], w, h, nch, bit_depth, o, l, imgs[(size_t)m], sq);
-        if (rc != FUIFGPU_OK) return rc;
+        rc = build_transformed_image(planes[m], w, h, nch, bit_depth, o, l, imgs[(size_t)m], sq, device_input);
         squeezed[(size_t)m] = sq ? 1 : 0;
     }
-    const int rc = write_streams_batch(imgs, nch, bit_depth, squeezed, o, blobs_out, sizes_out);
+    if (rc != FUIFGPU_OK) {   // (the pictures before the failed one may hold device-only channels)
+        for (Image &im : imgs) for (Chan &c : im.ch) { if (c.dev) fuifgpu_dev_free(c.dev); c.dev = nullptr; }
+        return rc;
+    }
+    rc = write_streams_batch(imgs, nch, bit_depth, squeezed, o, blobs_out, sizes_out);
     if (rc != FUIFGPU_OK) for (int m = 0; m < n_images; m++) { free(blobs_out[m]); blobs_out[m] = nullptr; sizes_out[m] = 0; }
     return rc;
+}
+extern "C" int fuifgpu_encode_images_lossy(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth,
+                                           const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out) {
+    return encode_images_common(planes, n_images, w, h, nch, bit_depth, opt, lossy, blobs_out, sizes_out, false);
 }
 extern "C" int fuifgpu_encode_images(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
                                      uint8_t **blobs_out, size_t *sizes_out) {
     return fuifgpu_encode_images_lossy(planes, n_images, w, h, nch, bit_depth, opt, nullptr, blobs_out, sizes_out);
+}
+extern "C" int fuifgpu_encode_images_device(const int32_t *const *planes_device, int n_images, int w, int h, int nch, int bit_depth,
+                                            const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out) {
+    return encode_images_common(planes_device, n_images, w, h, nch, bit_depth, opt, lossy, blobs_out, sizes_out, true);
 }

@@ -322,7 +322,8 @@ int fuifgpu_encode_image(const int32_t *planes, int w, int h, int nch, int bit_d
  * k_maniac_decode runs one wavefront per group of a batch) -- and the host assembles the streams.  blobs_out[m] / sizes_out[m]
  * are what fuifgpu_encode_image writes for picture m, byte for byte (gpu_entropy is implied; opt NULL = CLI defaults).
  * A picture in flight holds its channels on the host and on the device plus 12 bytes of coder scratch per sample (~0.5 GB per 4K
- * RGB picture): the caller sizes its batches to the device (fuifgpu_dev_mem_info) and chunks larger sets.
+ * RGB picture): the caller sizes its batches to the device (fuifgpu_dev_mem_info) and chunks larger sets.  fuifgpu_encode_images_device
+ * holds no host copy of a picture at all (4 + 12 bytes per sample on the device, and on the host one picture's learner samples at a time).
  * Replaces N runs of the reference's `fuif_encode_file` (encoding/encoding.cpp:727-735). */
 int fuifgpu_encode_images(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
                           uint8_t **blobs_out, size_t *sizes_out);
@@ -349,6 +350,25 @@ int fuifgpu_encode_image_lossy(const int32_t *planes, int w, int h, int nch, int
                                const fuifgpu_lossy_options *lossy, uint8_t **blob_out, size_t *size_out);
 int fuifgpu_encode_images_lossy(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
                                 const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out);
+/* ---- pictures that already live in device memory (a renderer's output, a torch tensor, a decoded batch's output slab) ----
+ * planes_device[m]: nch planes of w*h int32 in DEVICE memory of the calling thread's current device (values in [0, 2^bit_depth-1]);
+ * they are read, never written, and stay the caller's.  Same bytes as fuifgpu_encode_images_lossy for the same samples and options;
+ * gpu_forward and gpu_entropy are implied.  lossy == NULL: lossless.  Synchronous (null stream), like the other encode calls.
+ * The planes are copied device-to-device into working buffers, the forward transforms run there, and the transformed channels stay
+ * on the device until the last coded byte: their ranges and zero counts come from one statistics launch, the tree learner's samples
+ * from one launch per picture, and only a group that is rolled back to "uncompressed" (encoding.cpp:545-551) comes to the host.
+ * Without a HIP device: FUIFGPU_E_HIP (no host route).  A NULL planes_device[m] is FUIFGPU_E_ARG and leaves every blobs_out[m] NULL.
+ * Found by symbol lookup, like the three entry points below it: the ABI version does not change. */
+int fuifgpu_encode_images_device(const int32_t *const *planes_device, int n_images, int w, int h, int nch, int bit_depth,
+                                 const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy,
+                                 uint8_t **blobs_out, size_t *sizes_out);
+/* one plane's {min, max, number of zero samples} accumulated into stats3_device (device memory the caller presets, e.g.
+ * INT32_MAX, INT32_MIN, 0); the plane is only read.  n_samples == 0 touches nothing; n_samples < 0 or > INT32_MAX (the count is an
+ * int32), or a NULL pointer with n_samples > 0: FUIFGPU_E_ARG.  Asynchronous on stream */
+int fuifgpu_channel_stats(const int32_t *plane_device, int64_t n_samples, int32_t *stats3_device, void *stream);
+/* diagnostic: bytes of whole sample planes/channels the LAST encode call of this thread copied host->device and device->host
+ * (tables, trees, job records, learner samples, coder state and coded bytes are not planes and are not counted) */
+int fuifgpu_encode_plane_traffic(uint64_t *h2d_bytes, uint64_t *d2h_bytes);
 /* host: the constant fuif.cpp:459-503 gives one channel -- squeeze_option = opt->squeeze (the OPTION, not whether the picture was large
  * enough to be squeezed), chroma_table = 1 for the chroma table, shift = hcshift + vcshift (capped at 15).  1 when both qualities are
  * >= 100.  A negative shift or a quality the entry points above refuse gives -FUIFGPU_E_ARG. */

@@ -135,6 +135,11 @@ int readfirstlane(int v) {
     return v;
 }
 int bpermute(int byte_addr, int v) { return (int)exchange(v).v[(byte_addr >> 2) & 63]; }
+// lane ^ mask of the caller's own wavefront (a workgroup of 256 is four of them; mask < 64 stays inside one)
+int shfl_xor(int v, int lane_mask) {
+    const unsigned lane = fibers[cur].tid[0];
+    return (int)exchange(v).v[lane ^ ((unsigned)lane_mask & 63u)];
+}
 unsigned long long ballot(bool pr) {
     Exchanged e = exchange(pr ? 1 : 0);
     unsigned long long m = 0;

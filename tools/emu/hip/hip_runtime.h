@@ -45,6 +45,7 @@ void sync();
 int readlane(int v, int lane);
 int readfirstlane(int v);
 int bpermute(int byte_addr, int v);
+int shfl_xor(int v, int lane_mask);
 unsigned long long ballot(bool p);
 bool any(bool p);
 }  // namespace emu
@@ -56,6 +57,7 @@ static const emu::Triple threadIdx = {{0}, {1}, {2}}, blockIdx = {{3}, {4}, {5}}
 #define __builtin_amdgcn_readfirstlane(v) emu::readfirstlane(v)
 #define __builtin_amdgcn_readlane(v, l) emu::readlane((v), (l))
 #define __builtin_amdgcn_ds_bpermute(a, v) emu::bpermute((a), (v))
+#define __shfl_xor(v, m) emu::shfl_xor((v), (m))
 #define __builtin_amdgcn_s_sleep(n) emu::yield()
 #define __builtin_readcyclecounter() 0ull
 #define __ballot(p) emu::ballot(p)
@@ -72,6 +74,11 @@ template <class T> static inline T atomicCAS(T *p, T expected, T desired) { __at
 template <class T> static inline T atomicMax(T *p, T v) {
     T o = __atomic_load_n(p, __ATOMIC_SEQ_CST);
     while (v > o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {}
+    return o;
+}
+template <class T> static inline T atomicMin(T *p, T v) {
+    T o = __atomic_load_n(p, __ATOMIC_SEQ_CST);
+    while (v < o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {}
     return o;
 }
 // round-to-nearest without contraction: the emulator is built with -ffp-contract=off
