@@ -96,6 +96,19 @@ class LossyOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("quality", C.c_float), ("chroma_quality", C.c_float)]
 
 
+class PaletteOptions(C.Structure):
+    """fuifgpu_palette_options (include/fuifgpu.h): what `fuif -K colours -X percent -Y percent` sets; versioned by its first field"""
+    _fields_ = [("struct_size", C.c_uint32), ("palette_colors", C.c_int32), ("compact_post_percent", C.c_float), ("compact_pre_percent", C.c_float)]
+
+
+def make_palette_options(palette_colors=0, compact_post=0.0, compact_pre=0.0):
+    """PaletteOptions for the three keywords of encode_image / encode_images / encode_images_device, or None when all three are off
+    (the callers then use the entry points that have no palette argument)"""
+    if not palette_colors and not compact_post and not compact_pre:
+        return None
+    return PaletteOptions(C.sizeof(PaletteOptions), int(palette_colors), float(compact_post), float(compact_pre))
+
+
 def make_lossy_options(quality=None, chroma_quality=None):
     """LossyOptions for the two keywords of encode_image / encode_images: a missing quality is 100 (lossless luma), a missing
     chroma quality "same as quality" (the CLI's default, 101)"""
@@ -121,6 +134,7 @@ ABI_SYMBOLS = [
     "fuifgpu_dev_alloc", "fuifgpu_dev_free", "fuifgpu_dev_upload", "fuifgpu_dev_download",
     "fuifgpu_encode_image_lossy", "fuifgpu_encode_images_lossy", "fuifgpu_quantization_constant",
     "fuifgpu_encode_images_device", "fuifgpu_channel_stats", "fuifgpu_encode_plane_traffic",
+    "fuifgpu_encode_image_ex", "fuifgpu_encode_images_ex", "fuifgpu_fwd_palette",
     "fuifgpu_plane_checksums", "fuifgpu_device_count", "fuifgpu_set_device", "fuifgpu_get_device", "fuifgpu_batch_device", "fuifgpu_peer_copy", "fuifgpu_batch_set_in_flight",
 ]
 
@@ -223,6 +237,9 @@ def lib():
     L.fuifgpu_encode_images_lossy.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.fuifgpu_encode_images_device.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.fuifgpu_channel_stats.argtypes = [vp, C.c_int64, vp, vp]
+    L.fuifgpu_encode_image_ex.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(PaletteOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.fuifgpu_encode_images_ex.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(PaletteOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.fuifgpu_fwd_palette.argtypes = [C.POINTER(vp), C.c_int, C.c_int64, C.c_int, vp, vp, C.POINTER(C.c_int), vp]
     L.fuifgpu_encode_plane_traffic.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.fuifgpu_quantization_constant.argtypes = [C.c_float, C.c_float, C.c_int, C.c_int, C.c_int]
     L.fuifgpu_encode_image.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
@@ -492,8 +509,11 @@ DEFAULT_SPLIT_BITS = 0
 
 
 def encode_image(planes, bit_depth=8, ycocg=True, squeeze=True, max_properties=12, tree_mode=1, max_tree_nodes=4095, index=False,
-                 split_bits=None, gpu_forward=False, gpu_entropy=False, quality=None, chroma_quality=None):
+                 split_bits=None, gpu_forward=False, gpu_entropy=False, quality=None, chroma_quality=None, palette_colors=0, compact_post=0.0,
+                 compact_pre=0.0):
     """(C,H,W) int32 planes -> .fuif bytes (host C++ writer, csrc/writer.cpp); lossless unless a quality is given.
+    palette_colors / compact_post / compact_pre: `fuif -K / -X / -Y` (the CLI's defaults are 256, 70, 70; 0 = off, the default here): the
+    whole-picture Palette and the per-channel compaction the CLI tries for PNM input (fuifgpu_encode_image_ex).
     quality / chroma_quality: the two numbers of `fuif -Q` (0..100; chroma_quality None or > 100 = same as quality): the channels are
     quantised after YCoCg and Squeeze with the reference CLI's constants (fuifgpu_encode_image_lossy); 100 writes the lossless bytes.
     index=True appends the group index trailer (csrc/index.cpp) that unlocks one-wavefront-per-group decoding.
@@ -505,7 +525,11 @@ def encode_image(planes, bit_depth=8, ycocg=True, squeeze=True, max_properties=1
     opt = make_encode_options(int(ycocg), int(squeeze), max_properties, tree_mode, max_tree_nodes, int(index), int(split_bits), int(gpu_forward), int(gpu_entropy))
     out = C.c_void_p()
     n = C.c_size_t(0)
-    if quality is None and chroma_quality is None:
+    pal = make_palette_options(palette_colors, compact_post, compact_pre)
+    if pal is not None:
+        lossy = None if quality is None and chroma_quality is None else C.byref(make_lossy_options(quality, chroma_quality))
+        _check(lib().fuifgpu_encode_image_ex(planes.ctypes.data, w, h, c, bit_depth, C.byref(opt), lossy, C.byref(pal), C.byref(out), C.byref(n)))
+    elif quality is None and chroma_quality is None:
         _check(lib().fuifgpu_encode_image(planes.ctypes.data, w, h, c, bit_depth, C.byref(opt), C.byref(out), C.byref(n)))
     else:
         lossy = make_lossy_options(quality, chroma_quality)
@@ -516,7 +540,7 @@ def encode_image(planes, bit_depth=8, ycocg=True, squeeze=True, max_properties=1
 
 
 def encode_images(images, bit_depth=8, ycocg=True, squeeze=True, max_properties=12, tree_mode=1, max_tree_nodes=4095, index=False,
-                  split_bits=None, gpu_forward=False, quality=None, chroma_quality=None):
+                  split_bits=None, gpu_forward=False, quality=None, chroma_quality=None, palette_colors=0, compact_post=0.0, compact_pre=0.0):
     """a batch of equally sized (C,H,W) pictures -> list of .fuif byte strings, what encode_image writes for each of them; the
     MANIAC pixel loops of ALL their channel groups run in one launch pair on the GPU (fuifgpu_encode_images; with a quality,
     fuifgpu_encode_images_lossy)"""
@@ -530,7 +554,11 @@ def encode_images(images, bit_depth=8, ycocg=True, squeeze=True, max_properties=
     ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
     outs = (C.c_void_p * n)()
     sizes = (C.c_size_t * n)()
-    if quality is None and chroma_quality is None:
+    pal = make_palette_options(palette_colors, compact_post, compact_pre)
+    if pal is not None:   # (pictures of one batch may end up with different transform chains)
+        lossy = None if quality is None and chroma_quality is None else C.byref(make_lossy_options(quality, chroma_quality))
+        _check(lib().fuifgpu_encode_images_ex(ptrs, 0, n, w, h, c, bit_depth, C.byref(opt), lossy, C.byref(pal), outs, sizes))
+    elif quality is None and chroma_quality is None:
         _check(lib().fuifgpu_encode_images(ptrs, n, w, h, c, bit_depth, C.byref(opt), outs, sizes))
     else:
         lossy = make_lossy_options(quality, chroma_quality)
@@ -543,7 +571,7 @@ def encode_images(images, bit_depth=8, ycocg=True, squeeze=True, max_properties=
 
 
 def encode_images_device(planes, w=None, h=None, nch=None, bit_depth=8, ycocg=True, squeeze=True, max_properties=12, tree_mode=1, max_tree_nodes=4095,
-                         index=False, split_bits=None, quality=None, chroma_quality=None):
+                         index=False, split_bits=None, quality=None, chroma_quality=None, palette_colors=0, compact_post=0.0, compact_pre=0.0):
     """pictures that already live in DEVICE memory -> list of .fuif byte strings, the bytes encode_images writes for the same samples
     (fuifgpu_encode_images_device: the planes are read, never written, and no channel crosses to the host unless its group is rolled
     back to "uncompressed").  planes: a list of integer device pointers (each nch planes of w*h int32; w, h, nch given), or an object
@@ -565,7 +593,11 @@ def encode_images_device(planes, w=None, h=None, nch=None, bit_depth=8, ycocg=Tr
     arr = (C.c_void_p * max(n, 1))(*ptrs)
     outs = (C.c_void_p * max(n, 1))()
     sizes = (C.c_size_t * max(n, 1))()
-    _check(lib().fuifgpu_encode_images_device(arr, n, int(w), int(h), int(nch), bit_depth, C.byref(opt), lossy, outs, sizes))
+    pal = make_palette_options(palette_colors, compact_post, compact_pre)
+    if pal is not None:   # (the index planes stay on the device like every other channel; the palettes are small host tables)
+        _check(lib().fuifgpu_encode_images_ex(arr, 1, n, int(w), int(h), int(nch), bit_depth, C.byref(opt), lossy, C.byref(pal), outs, sizes))
+    else:
+        _check(lib().fuifgpu_encode_images_device(arr, n, int(w), int(h), int(nch), bit_depth, C.byref(opt), lossy, outs, sizes))
     blobs = []
     for k in range(n):
         blobs.append(C.string_at(outs[k], sizes[k]))
@@ -598,6 +630,20 @@ def fwd_quantize(plane_device_ptr, n_samples, q, minmax_device_ptr=None, stream=
     """fuifgpu_fwd_quantize: n int32 samples in DEVICE memory divided by q in place (truncating); their {min, max} accumulated
     into two int32 of device memory when a pointer is given"""
     _check(lib().fuifgpu_fwd_quantize(plane_device_ptr, int(n_samples), int(q), minmax_device_ptr, stream))
+
+
+def fwd_palette(plane_device_ptrs, n_samples, max_colors, index_device_ptr, stream=None):
+    """fuifgpu_fwd_palette: the forward Palette (transform/palette.h:92-142) of up to four planes of n int32 samples in DEVICE memory.
+    Returns None when they hold more than max_colors distinct tuples (nothing is written); otherwise the palette as a (planes, colours)
+    int32 array in the reference's order, with every sample's colour number written to index_device_ptr (which may be the first plane)."""
+    nb = len(plane_device_ptrs)
+    ptrs = (C.c_void_p * max(nb, 1))(*[int(p) if p else 0 for p in plane_device_ptrs])
+    pal = np.zeros((max(nb, 1), max(int(max_colors), 1)), dtype=np.int32)
+    count = C.c_int(0)
+    _check(lib().fuifgpu_fwd_palette(ptrs, nb, int(n_samples), int(max_colors), index_device_ptr, pal.ctypes.data, C.byref(count), stream))
+    if count.value < 0:
+        return None
+    return np.ascontiguousarray(pal[:nb, :count.value])
 
 
 def index_parse(blob):

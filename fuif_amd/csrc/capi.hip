@@ -193,6 +193,95 @@ int channel_stats_gpu(const StatsRec *recs, int n_recs, int32_t *stats_host) {
     if (e != hipSuccess) return hip_fail(e, "channel_stats_gpu");
     return FUIFGPU_OK;
 }
+// The writer's forward Palette (transforms.hip): collect on the GPU, bring back the few colours (never the samples), order them like the
+// reference's std::set on the host, send the ranks, index on the GPU.  One device buffer per call holds the table / bitmap and its words.
+int fwd_palette_gpu(const int32_t *const *planes_device, int nb, int64_t n, int max_colors, int32_t *index_device, std::vector<int32_t> &rows,
+                    int *n_colors, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!n_colors || nb < 1 || nb > 4 || n < 0 || max_colors < 0) return FUIFGPU_E_ARG;
+    *n_colors = -1;
+    rows.clear();
+    if (n == 0) { *n_colors = 0; return FUIFGPU_OK; }
+    if (!planes_device || !index_device) return FUIFGPU_E_ARG;
+    PalettePlanes pp{};
+    pp.nb = nb;
+    for (int c = 0; c < nb; c++) { if (!planes_device[c]) return FUIFGPU_E_ARG; pp.p[c] = planes_device[c]; }
+    if (max_colors < 1) return FUIFGPU_OK;
+    struct DevBuf { uint8_t *p = nullptr; ~DevBuf() { if (p) hipFree(p); } } buf;
+    uint32_t ctl[4] = {0, 0, 0, 0};
+    if (nb == 1) {
+        constexpr size_t W = 2048;   // bitmap words; layout: bitmap, prefix, ctl
+        HIPCHK(hipMalloc((void **)&buf.p, sizeof(uint32_t) * (2 * W + 4)));
+        uint32_t *d_bitmap = reinterpret_cast<uint32_t *>(buf.p), *d_ctl = d_bitmap + 2 * W;
+        int32_t *d_prefix = reinterpret_cast<int32_t *>(d_bitmap + W);
+        HIPCHK(hipMemsetAsync(buf.p, 0, sizeof(uint32_t) * (2 * W + 4), stream));
+        launch_palette_collect1(pp.p[0], n, d_bitmap, d_ctl, stream);
+        HIPCHK(hipGetLastError());
+        std::vector<uint32_t> bitmap(W);
+        HIPCHK(hipMemcpyAsync(bitmap.data(), d_bitmap, sizeof(uint32_t) * W, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (ctl[3]) return fail_msg(FUIFGPU_E_ARG, "fwd_palette: a sample outside the int16 range");
+        std::vector<int32_t> prefix(W);
+        int64_t count = 0;
+        for (size_t w = 0; w < W; w++) { prefix[w] = (int32_t)count; count += __builtin_popcount(bitmap[w]); }
+        if (count > max_colors) return FUIFGPU_OK;
+        rows.reserve((size_t)count);
+        for (size_t w = 0; w < W; w++)
+            for (uint32_t m = bitmap[w]; m; m &= m - 1) rows.push_back((int32_t)(32 * w + (size_t)__builtin_ctz(m)) - 32768);
+        HIPCHK(hipMemcpyAsync(d_prefix, prefix.data(), sizeof(int32_t) * W, hipMemcpyHostToDevice, stream));
+        launch_palette_index1(pp.p[0], n, d_bitmap, d_prefix, index_device, stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));
+        *n_colors = (int)count;
+        return FUIFGPU_OK;
+    }
+    // more colours than samples cannot be: the table is sized by what can occur, at least twice that (and a power of two)
+    const uint32_t limit = (uint32_t)std::min<int64_t>(max_colors, n);
+    if (limit > (1u << 26)) return fail_msg(FUIFGPU_E_ARG, "fwd_palette: more than 2^26 colours of several channels are not supported");   // (a 2 GB table)
+    uint32_t capacity = 1024;
+    while (capacity < 2 * (uint64_t)limit + 1024) capacity <<= 1;
+    const size_t keys_bytes = sizeof(unsigned long long) * capacity, rank_bytes = sizeof(int32_t) * capacity;   // layout: keys, ranks, ctl
+    HIPCHK(hipMalloc((void **)&buf.p, keys_bytes + rank_bytes + sizeof(ctl)));
+    unsigned long long *d_keys = reinterpret_cast<unsigned long long *>(buf.p);
+    int32_t *d_rank = reinterpret_cast<int32_t *>(buf.p + keys_bytes);
+    uint32_t *d_ctl = reinterpret_cast<uint32_t *>(buf.p + keys_bytes + rank_bytes);
+    HIPCHK(hipMemsetAsync(buf.p, 0, keys_bytes + rank_bytes + sizeof(ctl), stream));
+    launch_palette_collect(pp, n, d_keys, capacity, limit, d_ctl, stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (ctl[3]) return fail_msg(FUIFGPU_E_ARG, "fwd_palette: a sample outside the int16 range");
+    if (ctl[1] || ctl[0] > limit) return FUIFGPU_OK;
+    std::vector<unsigned long long> keys(capacity);
+    HIPCHK(hipMemcpyAsync(keys.data(), d_keys, keys_bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    // the set's order: lexicographic, component 0 most significant, signed (palette.h:103); slot -1 = the key 0
+    std::vector<std::pair<unsigned long long, int64_t>> found;
+    auto order_key = [nb](unsigned long long key) {
+        unsigned long long o = 0;
+        for (int c = 0; c < nb; c++) o = (o << 16) | (uint16_t)((int16_t)(key >> (16 * c)) + 32768);
+        return o;
+    };
+    if (ctl[2]) found.push_back({order_key(0), -1});
+    for (uint32_t s = 0; s < capacity; s++) if (keys[s]) found.push_back({order_key(keys[s]), (int64_t)s});
+    if (found.size() != ctl[0]) return fail_msg(FUIFGPU_E_HIP, "fwd_palette: the colour table and its counter disagree");
+    std::sort(found.begin(), found.end());
+    const size_t count = found.size();
+    std::vector<int32_t> rank(capacity, 0);
+    int32_t zero_rank = 0;
+    rows.assign(count * (size_t)nb, 0);
+    for (size_t k = 0; k < count; k++) {
+        if (found[k].second < 0) zero_rank = (int32_t)k; else rank[(size_t)found[k].second] = (int32_t)k;
+        for (int c = 0; c < nb; c++) rows[(size_t)c * count + k] = (int32_t)((found[k].first >> (16 * (nb - 1 - c))) & 0xFFFF) - 32768;
+    }
+    HIPCHK(hipMemcpyAsync(d_rank, rank.data(), rank_bytes, hipMemcpyHostToDevice, stream));
+    launch_palette_index(pp, n, d_keys, d_rank, capacity, zero_rank, index_device, stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    *n_colors = (int)count;
+    return FUIFGPU_OK;
+}
 int dev_copy(void *dst_device, const void *src_device, size_t bytes) {
     if (bytes) HIPCHK(hipMemcpy(dst_device, src_device, bytes, hipMemcpyDeviceToDevice));
     return FUIFGPU_OK;
@@ -1121,6 +1210,15 @@ int fuifgpu_channel_stats(const int32_t *plane_device, int64_t n_samples, int32_
     const int blocks = channel_stats_blocks(n_samples);
     launch_channel_stats(nullptr, 1, StatsRec{plane_device, n_samples, 0, blocks}, blocks, stats3_device, (hipStream_t)stream);   // (no launch for n_samples == 0)
     HIPCHK(hipGetLastError());
+    return FUIFGPU_OK;
+}
+int fuifgpu_fwd_palette(const int32_t *const *planes_device, int nb, int64_t n_samples, int max_colors, int32_t *index_device, int32_t *palette_host,
+                        int *n_colors, void *stream) {
+    if (!n_colors || (n_samples > 0 && max_colors > 0 && !palette_host)) return FUIFGPU_E_ARG;
+    std::vector<int32_t> rows;
+    const int rc = fwd_palette_gpu(planes_device, nb, n_samples, max_colors, index_device, rows, n_colors, stream);
+    if (rc != FUIFGPU_OK || *n_colors <= 0) return rc;
+    for (int c = 0; c < nb; c++) memcpy(palette_host + (size_t)c * max_colors, rows.data() + (size_t)c * *n_colors, sizeof(int32_t) * (size_t)*n_colors);
     return FUIFGPU_OK;
 }
 // a plane anywhere in device memory as an element offset from a null base (every plane pointer is 4-byte aligned)

@@ -184,6 +184,11 @@ struct StatsRec {
 // every record in one launch and the triples back with one copy (capi.hip): stats_host gets n_recs triples, each preset to what
 // Chan::minmax gives an empty channel ({INT32_MAX, INT32_MIN + 1, 0})
 int channel_stats_gpu(const StatsRec *recs, int n_recs, int32_t *stats_host);
+// The writer's forward Palette on device planes (capi.hip; transforms.hip k_palette_collect / k_palette_index): the distinct tuples of
+// planes[0..nb-1] (nb 1..4, n samples each).  More than max_colors: *n_colors = -1 and nothing is written.  Otherwise rows = the palette
+// (rows[c * *n_colors + k], the reference's order) and index_device[i] = the colour of sample i (may alias planes[0]).  Synchronous
+int fwd_palette_gpu(const int32_t *const *planes_device, int nb, int64_t n, int max_colors, int32_t *index_device, std::vector<int32_t> &rows,
+                    int *n_colors, void *stream = nullptr);
 // device -> device copy on the null stream (the writer's working copies of caller-owned planes)
 int dev_copy(void *dst_device, const void *src_device, size_t bytes);
 

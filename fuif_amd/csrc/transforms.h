@@ -48,5 +48,18 @@ void launch_fwd_quantize(const QuantChan *dev_table, int n_channels, int total_b
 // record `one` (first_block 0) into dev_stats
 int channel_stats_blocks(int64_t n_samples);
 void launch_channel_stats(const StatsRec *dev_table, int n_recs, StatsRec one, int total_blocks, int32_t *dev_stats, hipStream_t stream);
+// forward Palette (transform/palette.h:92-142).  Several channels: the distinct tuples of nb planes into an open-addressing table of
+// `capacity` (a power of two > 2 * limit) zero-initialised 64-bit keys; dev_ctl: four zero-initialised words {distinct colours, too many,
+// the all-zero key occurs, a sample outside int16}.  Then every sample's colour number from the table and the ranks of its slots.
+// One channel: a zero-initialised presence bitmap of 2048 words over the int16 range, then prefix[w] + the set bits below the sample's own
+struct PalettePlanes {
+    const int32_t *p[4];
+    int32_t nb;
+};
+void launch_palette_collect(const PalettePlanes &pp, int64_t n, unsigned long long *dev_keys, uint32_t capacity, uint32_t limit, uint32_t *dev_ctl, hipStream_t stream);
+void launch_palette_index(const PalettePlanes &pp, int64_t n, const unsigned long long *dev_keys, const int32_t *dev_rank, uint32_t capacity, int32_t zero_rank,
+                          int32_t *index, hipStream_t stream);
+void launch_palette_collect1(const int32_t *plane, int64_t n, uint32_t *dev_bitmap, uint32_t *dev_ctl, hipStream_t stream);
+void launch_palette_index1(const int32_t *plane, int64_t n, const uint32_t *dev_bitmap, const int32_t *dev_prefix, int32_t *index, hipStream_t stream);
 
 }  // namespace fuifgpu

@@ -1092,6 +1092,132 @@ void launch_channel_stats(const StatsRec *dev_table, int n_recs, StatsRec one, i
     if (total_blocks <= 0) return;
     hipLaunchKernelGGL(k_channel_stats, dim3((unsigned)total_blocks), dim3(256), 0, stream, dev_table, n_recs, one, dev_stats);
 }
+// ---------------------------------------------------------------------------------------------
+// Forward Palette (transform/palette.h:92-142): which colour tuples occur, then every pixel's colour number.  The reference inserts every
+// pixel into a std::set and searches the palette linearly per pixel; here the set is built by all lanes at once and the order of the
+// colours (the set's: lexicographic, signed) is made by the host from the few colours found (capi.hip fwd_palette_gpu).
+// Every loop below is bounded: the grid-stride loops by n, a probe sequence by the capacity of the table.
+//
+// Several channels (2..4): the tuple's int16 components packed into 64 bits are the key of an open-addressing table in device memory
+// (linear probing, capacity a power of two of at least twice the limit), claimed with a 64-bit compare-and-swap on an empty slot.  Four
+// int16 fill the 64 bits, so no key can mean "empty": an empty slot holds 0 and the ONE tuple whose key is 0 is kept apart, in ctl[2].
+// The common case -- the colour is in the table already -- is one load; atomics happen once per distinct colour and lane that races for it.
+// ctl[0] counts the distinct colours; when it passes the limit ctl[1] is set and every lane stops at its next sample, so a photograph
+// costs one insert per lane in flight.  Those inserts can at most fill the table: a probe sequence looks at ctl[1] every 32 slots, and one
+// that has seen `capacity` slots ends and reports "too many" (a full table holds more than the limit).  ctl[3]: a sample outside int16.
+constexpr int PAL_CTL_COUNT = 0, PAL_CTL_TOO_MANY = 1, PAL_CTL_ZERO_KEY = 2, PAL_CTL_BAD_SAMPLE = 3;
+DEV bool palette_key(const PalettePlanes &pp, int64_t i, unsigned long long &key) {
+    key = 0;
+    bool ok = true;
+    for (int c = 0; c < pp.nb; c++) {
+        const int32_t v = pp.p[c][i];
+        ok &= (uint32_t)(v + 32768) < 65536u;
+        key |= (unsigned long long)(uint16_t)v << (16 * c);
+    }
+    return ok;
+}
+DEV uint32_t palette_slot(unsigned long long key, int shift) { return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> shift); }   // shift = 64 - log2(capacity)
+DEV void palette_count_one(uint32_t *ctl, uint32_t limit) {
+    if (atomicAdd(ctl + PAL_CTL_COUNT, 1u) + 1u > limit) atomicOr(ctl + PAL_CTL_TOO_MANY, 1u);
+}
+__global__ __launch_bounds__(256) void k_palette_collect(PalettePlanes pp, int64_t n, unsigned long long *keys, uint32_t cap_mask, int shift, uint32_t limit,
+                                                         uint32_t *ctl) {
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+        if (__hip_atomic_load(ctl + PAL_CTL_TOO_MANY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+        unsigned long long key;
+        if (!palette_key(pp, i, key)) { atomicOr(ctl + PAL_CTL_BAD_SAMPLE, 1u); return; }
+        if (key == 0) {
+            if (!__hip_atomic_load(ctl + PAL_CTL_ZERO_KEY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) && atomicOr(ctl + PAL_CTL_ZERO_KEY, 1u) == 0)
+                palette_count_one(ctl, limit);
+            continue;
+        }
+        uint32_t slot = palette_slot(key, shift) & cap_mask;
+        bool placed = false;
+        for (uint32_t probe = 0; probe <= cap_mask && !placed; probe++, slot = (slot + 1) & cap_mask) {
+            // a photograph: every lane in flight brings a colour of its own and the table fills; long probe sequences look at the verdict
+            if ((probe & 31) == 31 && __hip_atomic_load(ctl + PAL_CTL_TOO_MANY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+            unsigned long long cur = __hip_atomic_load(keys + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cur == 0) {
+                cur = atomicCAS(keys + slot, 0ull, key);
+                if (cur == 0) { palette_count_one(ctl, limit); placed = true; }
+            }
+            placed |= cur == key;
+        }
+        if (!placed) atomicOr(ctl + PAL_CTL_TOO_MANY, 1u);   // every slot holds another colour
+    }
+}
+// rank[slot]: the colour number of the key in that slot (zero_rank: of the key 0); index may be pp.p[0] -- a lane reads its tuple, then writes
+__global__ __launch_bounds__(256) void k_palette_index(PalettePlanes pp, int64_t n, const unsigned long long *keys, const int32_t *rank, uint32_t cap_mask,
+                                                       int shift, int32_t zero_rank, int32_t *index) {
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+        unsigned long long key;
+        palette_key(pp, i, key);
+        int32_t found = zero_rank;
+        if (key != 0) {
+            found = 0;   // (a key the collect pass has not seen cannot occur; it would end at an empty slot or after `capacity` probes)
+            uint32_t slot = palette_slot(key, shift) & cap_mask;
+            for (uint32_t probe = 0; probe <= cap_mask; probe++, slot = (slot + 1) & cap_mask) {
+                const unsigned long long cur = keys[slot];
+                if (cur == key) { found = rank[slot]; break; }
+                if (cur == 0) break;
+            }
+        }
+        index[i] = found;
+    }
+}
+// One channel (channel compaction): the limit reaches 0.7 x 65536 there, so the set is a presence bitmap over the int16 range -- 8 KB,
+// one per workgroup in LDS (a bit that is already set costs a read), OR-ed into the global one word by word at the end.  The colours are
+// its set bits in ascending order and a sample's colour number the count of set bits below its own: prefix[w] = set bits in words < w.
+constexpr int PAL_BITMAP_WORDS = 65536 / 32;
+__global__ __launch_bounds__(256) void k_palette_collect1(const int32_t *plane, int64_t n, uint32_t *bitmap, uint32_t *ctl) {
+    __shared__ uint32_t s_bits[PAL_BITMAP_WORDS];
+    for (int k = threadIdx.x; k < PAL_BITMAP_WORDS; k += blockDim.x) s_bits[k] = 0;
+    __syncthreads();
+    bool bad = false;
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+        const uint32_t u = (uint32_t)(plane[i] + 32768);
+        if (u >= 65536u) { bad = true; continue; }
+        const uint32_t m = 1u << (u & 31);
+        if (!(s_bits[u >> 5] & m)) atomicOr(&s_bits[u >> 5], m);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < PAL_BITMAP_WORDS; k += blockDim.x)
+        if (s_bits[k]) atomicOr(bitmap + k, s_bits[k]);
+    if (bad) atomicOr(ctl + PAL_CTL_BAD_SAMPLE, 1u);
+}
+__global__ __launch_bounds__(256) void k_palette_index1(const int32_t *plane, int64_t n, const uint32_t *bitmap, const int32_t *prefix, int32_t *index) {
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+        const uint32_t u = (uint32_t)(plane[i] + 32768) & 0xFFFFu;
+        index[i] = prefix[u >> 5] + (int32_t)__popcll((unsigned long long)(bitmap[u >> 5] & ((1u << (u & 31)) - 1u)));
+    }
+}
+// 2048 samples per block until 512 blocks fill the device (each block of the one-channel form ends with up to 2048 atomics)
+static unsigned palette_blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 2047) / 2048, 512)); }
+void launch_palette_collect(const PalettePlanes &pp, int64_t n, unsigned long long *dev_keys, uint32_t capacity, uint32_t limit, uint32_t *dev_ctl, hipStream_t stream) {
+    if (n <= 0) return;
+    int log2cap = 0;
+    while ((1u << log2cap) < capacity) log2cap++;
+    hipLaunchKernelGGL(k_palette_collect, dim3(palette_blocks(n)), dim3(256), 0, stream, pp, n, dev_keys, capacity - 1, 64 - log2cap, limit, dev_ctl);
+}
+void launch_palette_index(const PalettePlanes &pp, int64_t n, const unsigned long long *dev_keys, const int32_t *dev_rank, uint32_t capacity, int32_t zero_rank,
+                          int32_t *index, hipStream_t stream) {
+    if (n <= 0) return;
+    int log2cap = 0;
+    while ((1u << log2cap) < capacity) log2cap++;
+    hipLaunchKernelGGL(k_palette_index, dim3(palette_blocks(n)), dim3(256), 0, stream, pp, n, dev_keys, dev_rank, capacity - 1, 64 - log2cap, zero_rank, index);
+}
+void launch_palette_collect1(const int32_t *plane, int64_t n, uint32_t *dev_bitmap, uint32_t *dev_ctl, hipStream_t stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_palette_collect1, dim3(palette_blocks(n)), dim3(256), 0, stream, plane, n, dev_bitmap, dev_ctl);
+}
+void launch_palette_index1(const int32_t *plane, int64_t n, const uint32_t *dev_bitmap, const int32_t *dev_prefix, int32_t *index, hipStream_t stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_palette_index1, dim3(palette_blocks(n)), dim3(256), 0, stream, plane, n, dev_bitmap, dev_prefix, index);
+}
 void launch_fwd_ycocg(int32_t *c0, int32_t *c1, int32_t *c2, int64_t n, hipStream_t stream) {
     hipLaunchKernelGGL(k_fwd_ycocg,dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, c0, c1, c2, n);
 }

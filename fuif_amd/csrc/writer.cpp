@@ -3,7 +3,10 @@
 // the reference encoder needs ~19 s per 4K image and does not exist on
 // the GPU box, so the build carries its own writer.  It produces streams the REAL reference
 // decoder accepts (tests/test_writer.py decodes them with oracle/_ref and compares pixels) using
-// the same format decisions as the reference CLI for photographic PNM input:
+// the same format decisions as the reference CLI for PNM input:
+//   [with fuifgpu_palette_options, what the CLI tries by default for everything that is not a photograph: channel compaction before the
+//    colour transform, a Palette over all channels (or all but the last) behind it, channel compaction again (fuif.cpp:345-350, 374-430;
+//    transform/palette.h:92-142); palettes are meta-channels in front of the channel list, coded with predictor 3]
 //   YCoCg (transform/ycocg.h:65-95) -> default Squeeze (transform/squeeze.h:135-170,227-321)
 //   -> one channel per group (fuif.cpp:455), predictor 2 for the base channels and 0 for residuals
 //   (fuif.cpp:580-588), tight ranges (image/image.h:127), responsive offsets (image.cpp:124-136,
@@ -19,6 +22,8 @@
 // FUIF with realistic tree sizes but not byte-identical to the reference's.
 // fuifgpu_encode_images_device: the pictures are in device memory and the transformed channels stay there (Chan::resident); the host sees
 // three integers per channel (k_channel_stats) and the learner's samples (k_learn_samples_jobs), and writes the same bytes.
+// With a palette the colours are collected and the pixels indexed there too (k_palette_collect / k_palette_index): the index plane stays on
+// the device like any channel; the palette itself is a table the host sorts, not a plane, and fuifgpu_encode_plane_traffic does not count it.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -190,7 +195,8 @@ int smooth_tendency(int B, int a, int n) {  // transform/squeeze.h:61-77
 }
 
 void fwd_ycocg(Image &img) {  // transform/ycocg.h:65-95
-    Chan &c0 = img.ch[0], &c1 = img.ch[1], &c2 = img.ch[2];
+    const int m = img.nb_meta;
+    Chan &c0 = img.ch[m], &c1 = img.ch[m + 1], &c2 = img.ch[m + 2];
     size_t n = c0.data.size();
     for (size_t i = 0; i < n; i++) {
         int R = c0.data[i], G = c1.data[i], B = c2.data[i];
@@ -303,6 +309,100 @@ int fwd_squeeze(Image &img, const std::vector<int> &params, bool on_gpu = false)
         }
     }
     return FUIFGPU_OK;
+}
+
+// ---- forward Palette (transform/palette.h:92-142) and the three options of the CLI that try it (fuif.cpp:374-430) -----------------
+// colors: -K, the whole-picture palette; post / pre: -X / -Y as the CLI holds them, a float fraction of a channel's range (0.01 * percent,
+// computed in double and stored to float like `channel_colors = 0.01*atof(optarg)`); 0 = off
+struct PaletteOpts {
+    int colors = 0;
+    float post = 0.f, pre = 0.f;
+    bool any() const { return colors > 0 || post > 0.f || pre > 0.f; }
+};
+// a tuple as one integer whose order is the order of std::set<std::vector<pixel_type>>: component 0 most significant, signed
+inline uint64_t tuple_order_key(const Chan *chans, int nb, size_t i) {
+    uint64_t k = 0;
+    for (int c = 0; c < nb; c++) k = (k << 16) | (uint16_t)(chans[c].data[i] + 32768);
+    return k;
+}
+// the host's collect + index: `rows` gets the palette (row c = component c, colours in the reference's order) and channel `chans[0]` the
+// indices; false (nothing touched) with more than `limit` colours
+bool fwd_palette_host(Chan *chans, int nb, int limit, std::vector<int32_t> &rows, int &n_colors) {
+    const size_t n = chans[0].data.size();
+    std::vector<uint64_t> keys;   // the distinct tuples, kept sorted; a run of equal pixels costs one comparison each
+    uint64_t last = 0;
+    bool have = false;
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t k = tuple_order_key(chans, nb, i);
+        if (have && k == last) continue;
+        last = k; have = true;
+        auto at = std::lower_bound(keys.begin(), keys.end(), k);
+        if (at != keys.end() && *at == k) continue;
+        if (keys.size() >= (size_t)limit) return false;   // palette.h:109: one more than the limit
+        keys.insert(at, k);
+    }
+    n_colors = (int)keys.size();
+    rows.assign((size_t)n_colors * nb, 0);
+    for (int k = 0; k < n_colors; k++)
+        for (int c = 0; c < nb; c++) rows[(size_t)c * n_colors + k] = (int32_t)((keys[(size_t)k] >> (16 * (nb - 1 - c))) & 0xFFFF) - 32768;
+    have = false;
+    int32_t last_index = 0;
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t k = tuple_order_key(chans, nb, i);
+        if (!have || k != last) { last_index = (int32_t)(std::lower_bound(keys.begin(), keys.end(), k) - keys.begin()); last = k; have = true; }
+        chans[0].data[i] = last_index;
+    }
+    return true;
+}
+// Image::do_transform of one Palette attempt over channels begin..end (numbered from the first non-meta channel) with at most `limit`
+// colours: on success the index replaces channel `begin`, the others go, the palette (colours x nb, hshift -1) goes in FRONT of the channel
+// list and the transform is recorded with the number of colours found; on failure nothing changes and nothing is recorded.
+// on_gpu: the samples are on the device (Chan::dev); the palette itself is a small table and lives on the host either way
+int try_palette(Image &img, int begin, int end, int limit, bool on_gpu) {
+    const int bc = img.nb_meta + begin, nb = end - begin + 1;
+    if (limit < 1 || nb < 1 || !img.ch[bc].w || !img.ch[bc].h) return FUIFGPU_OK;   // (the first pixel is already one colour too many)
+    std::vector<int32_t> rows;
+    int n_colors = -1;
+    if (on_gpu) {
+        const int32_t *planes[4] = {nullptr, nullptr, nullptr, nullptr};
+        if (nb > 4) return FUIFGPU_E_ARG;
+        for (int c = 0; c < nb; c++) planes[c] = img.ch[bc + c].dev;
+        const int rc = fwd_palette_gpu(planes, nb, (int64_t)img.ch[bc].w * img.ch[bc].h, limit, img.ch[bc].dev, rows, &n_colors);
+        if (rc != FUIFGPU_OK) return rc;
+    } else if (!fwd_palette_host(&img.ch[bc], nb, limit, rows, n_colors)) n_colors = -1;
+    if (n_colors < 0) return FUIFGPU_OK;
+    for (int c = 1; c < nb; c++) { if (img.ch[bc + c].dev) fuifgpu_dev_free(img.ch[bc + c].dev); }
+    img.ch.erase(img.ch.begin() + bc + 1, img.ch.begin() + bc + nb);
+    Chan pal;   // Channel pch(nb_colors, nb, 0, 1); pch.hshift = -1
+    pal.w = n_colors; pal.h = nb; pal.minval = 0; pal.maxval = 1; pal.hshift = -1;
+    pal.data = std::move(rows);
+    img.ch.insert(img.ch.begin(), std::move(pal));
+    img.nb_meta++;
+    img.nb_channels -= nb - 1;
+    img.transforms.push_back({TR_PALETTE, {begin, end, n_colors}});
+    return FUIFGPU_OK;
+}
+// Image::recompute_minmax for the channels the compaction heuristic looks at (the non-meta ones): host scan, or one k_channel_stats launch
+int current_ranges(Image &img, bool on_gpu) {
+    if (!on_gpu) { for (int i = img.nb_meta; i < (int)img.ch.size(); i++) img.ch[i].minmax(); return FUIFGPU_OK; }
+    std::vector<StatsRec> recs;
+    for (int i = img.nb_meta; i < (int)img.ch.size(); i++) recs.push_back(StatsRec{img.ch[i].dev, (int64_t)img.ch[i].w * img.ch[i].h, 0, 0});
+    std::vector<int32_t> stats(3 * recs.size());
+    const int rc = channel_stats_gpu(recs.data(), (int)recs.size(), stats.data());
+    for (size_t k = 0; k < recs.size() && rc == FUIFGPU_OK; k++) { img.ch[img.nb_meta + k].minval = stats[3 * k]; img.ch[img.nb_meta + k].maxval = stats[3 * k + 1]; }
+    return rc;
+}
+// fuif.cpp:374-388 (pre: before the colour transform, ranges of 256 values and more only) and :418-430 (after it): every channel whose
+// samples use less than `fraction` of its range is compacted to the ranks of the values that occur
+int compact_channels(Image &img, float fraction, bool pre, bool on_gpu) {
+    int rc = current_ranges(img, on_gpu);
+    for (int i = 0; i < img.nb_channels && rc == FUIFGPU_OK; i++) {
+        const Chan &c = img.ch[img.nb_meta + i];
+        const int colors = c.maxval - c.minval + 1;
+        if (pre && colors < 256) continue;
+        rc = try_palette(img, i, i, (int)(fraction * colors), on_gpu);
+    }
+    return rc;
 }
 
 // ---- lossy: the CLI's quantisation constants for Squeeze channels (fuif.cpp:459-503) ---------------------------------------------
@@ -547,6 +647,7 @@ int ensure_dev(const Chan &c) {
     if (c.dev || c.data.empty()) return FUIFGPU_OK;
     c.dev = (int32_t *)fuifgpu_dev_alloc(sizeof(int32_t) * c.data.size());
     if (!c.dev) return FUIFGPU_E_HIP;
+    if (c.hshift < 0) return fuifgpu_dev_upload(c.dev, c.data.data(), sizeof(int32_t) * c.data.size());   // a palette is a table, not a plane: not counted
     return plane_upload(c.dev, c.data.data(), c.data.size());
 }
 
@@ -754,8 +855,9 @@ int write_stream(Image &img, int nch, int bit_depth, bool squeezed, const fuifgp
 // on the host or on the GPU.  device_input: `planes` is device memory -- the forward transforms run on working copies there (gpu_forward is
 // implied) and the transformed channels STAY there, device-only (Chan::resident), for write_streams_batch
 static int build_transformed_image(const int32_t *planes, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options &o,
-                                   const fuifgpu::Lossy &lossy, fuifgpu::Image &img, bool &squeezed, bool device_input = false) {
+                                   const fuifgpu::Lossy &lossy, fuifgpu::PaletteOpts pal, fuifgpu::Image &img, bool &squeezed, bool device_input = false) {
     using namespace fuifgpu;
+    if (lossy.quality < 100.f && pal.colors > 0) pal = PaletteOpts();   // fuif.cpp:345-350: `quality` alone is read, and only -K > 0 clears the other two
     img.w = w; img.h = h; img.maxval = (1 << bit_depth) - 1; img.nb_channels = nch;
     img.ch.resize(nch);
     for (int c = 0; c < nch; c++) {
@@ -776,13 +878,20 @@ static int build_transformed_image(const int32_t *planes, int w, int h, int nch,
             ch.data.clear();
         }
     }
+    if (rc == FUIFGPU_OK && pal.pre > 0.f && o.ycocg) rc = compact_channels(img, pal.pre, true, on_gpu);   // fuif.cpp:374-388
     if (rc == FUIFGPU_OK && o.ycocg && nch >= 3) {
-        if (on_gpu) rc = fuifgpu_fwd_ycocg(img.ch[0].dev, img.ch[1].dev, img.ch[2].dev, w, h, nullptr);
+        const int m = img.nb_meta;
+        if (on_gpu) rc = fuifgpu_fwd_ycocg(img.ch[m].dev, img.ch[m + 1].dev, img.ch[m + 2].dev, w, h, nullptr);
         else fwd_ycocg(img);
         img.transforms.push_back({TR_YCOCG, {}});
     }
+    if (rc == FUIFGPU_OK && pal.colors > 0) {   // fuif.cpp:400-417: every channel, then (still more than three) all but the last
+        if (img.nb_channels > 1) rc = try_palette(img, 0, img.nb_channels - 1, pal.colors, on_gpu);
+        if (rc == FUIFGPU_OK && img.nb_channels > 3) rc = try_palette(img, 0, img.nb_channels - 2, pal.colors, on_gpu);
+    }
+    if (rc == FUIFGPU_OK && pal.post > 0.f) rc = compact_channels(img, pal.post, false, on_gpu);   // fuif.cpp:418-430
     squeezed = false;
-    if (rc == FUIFGPU_OK && o.squeeze && (int64_t)w * h > 20) {  // fuif.cpp:452
+    if (rc == FUIFGPU_OK && o.squeeze && (int64_t)img.ch[0].w * img.ch[0].h > 20) {  // fuif.cpp:453: channel[0] -- a palette, once there is one
         std::vector<int> params = default_squeeze_params(img);
         rc = fwd_squeeze(img, params, on_gpu);
         img.transforms.push_back({TR_SQUEEZE, {}});  // empty parameter list = "default" in the stream
@@ -831,6 +940,24 @@ static bool read_lossy_options(const fuifgpu_lossy_options *lossy, Lossy &l) {
     return read_qualities(lossy->quality, sz >= sizeof(fuifgpu_lossy_options) ? lossy->chroma_quality : 101.f, l);
 }
 
+// fuifgpu_palette_options is versioned like the other two; NULL, or fields the caller's struct ends before, = 0 = off
+static bool read_palette_options(const fuifgpu_palette_options *palette, int nch, PaletteOpts &p) {
+    p = PaletteOpts();
+    if (!palette) return true;
+    const uint32_t sz = palette->struct_size;
+    if (sz < sizeof(uint32_t) || (sz & 3u)) return false;
+    fuifgpu_palette_options v;
+    memset(&v, 0, sizeof(v));
+    memcpy(&v, palette, sz < sizeof(v) ? sz : sizeof(v));
+    if (v.palette_colors < 0 || v.palette_colors > 32767) return false;   // an index is an int16 sample
+    if (!(v.compact_post_percent >= 0.f && v.compact_post_percent <= 100.f) || !(v.compact_pre_percent >= 0.f && v.compact_pre_percent <= 100.f)) return false;
+    if (v.palette_colors > 0 && nch > 4) return false;   // the colour tuples are keys of at most four int16 (no PNM has more channels)
+    p.colors = v.palette_colors;
+    p.post = 0.01 * (double)v.compact_post_percent;   // fuif.cpp:143-144
+    p.pre = 0.01 * (double)v.compact_pre_percent;
+    return true;
+}
+
 int fuifgpu_encode_plane_traffic(uint64_t *h2d_bytes, uint64_t *d2h_bytes) {
     if (h2d_bytes) *h2d_bytes = g_plane_h2d;
     if (d2h_bytes) *d2h_bytes = g_plane_d2h;
@@ -844,12 +971,13 @@ int fuifgpu_quantization_constant(float quality, float chroma_quality, int squee
 }
 
 // planes: nch planes of w*h int32 in [0, 2^bit_depth-1].
-int fuifgpu_encode_image_lossy(const int32_t *planes, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
-                               const fuifgpu_lossy_options *lossy, uint8_t **blob_out, size_t *size_out) {
+int fuifgpu_encode_image_ex(const int32_t *planes, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
+                            const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette, uint8_t **blob_out, size_t *size_out) {
     if (!planes || !blob_out || !size_out || w < 1 || h < 1 || nch < 1 || nch > 8 || bit_depth < 1 || bit_depth > 14) return FUIFGPU_E_ARG;
     fuifgpu_encode_options o;
     Lossy l;
-    if (!read_encode_options(opt, o, 0) || !read_lossy_options(lossy, l)) return FUIFGPU_E_ARG;
+    PaletteOpts pal;
+    if (!read_encode_options(opt, o, 0) || !read_lossy_options(lossy, l) || !read_palette_options(palette, nch, pal)) return FUIFGPU_E_ARG;
     if (o.max_properties < 0 || o.max_properties > 2 * kMaxRefs) return FUIFGPU_E_ARG;
     if (o.max_tree_nodes < 1) o.max_tree_nodes = 4095;
     if (o.max_tree_nodes > kMaxNodes) o.max_tree_nodes = kMaxNodes;
@@ -857,9 +985,13 @@ int fuifgpu_encode_image_lossy(const int32_t *planes, int w, int h, int nch, int
     g_plane_h2d = g_plane_d2h = 0;
     Image img;
     bool squeezed = false;
-    const int rc = build_transformed_image(planes, w, h, nch, bit_depth, o, l, img, squeezed);
+    const int rc = build_transformed_image(planes, w, h, nch, bit_depth, o, l, pal, img, squeezed);
     if (rc != FUIFGPU_OK) return rc;
     return write_stream(img, nch, bit_depth, squeezed, o, blob_out, size_out);
+}
+int fuifgpu_encode_image_lossy(const int32_t *planes, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
+                               const fuifgpu_lossy_options *lossy, uint8_t **blob_out, size_t *size_out) {
+    return fuifgpu_encode_image_ex(planes, w, h, nch, bit_depth, opt, lossy, nullptr, blob_out, size_out);
 }
 int fuifgpu_encode_image(const int32_t *planes, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt, uint8_t **blob_out,
                          size_t *size_out) {
@@ -938,6 +1070,7 @@ int channel_ranges(Image *imgs, size_t n_images) {
     return rc;
 }
 int group_predictor(const Image &img, int i, bool squeezed, bool dct_style) {  // fuif.cpp:580-588
+    if (i < img.nb_meta) return 3;   // "left" for the palettes
     if (!squeezed && !dct_style) return 2;
     return i < img.nb_meta + img.nb_channels ? 2 : 0;
 }
@@ -1153,11 +1286,13 @@ int write_streams_batch(std::vector<Image> &imgs, int nch, int bit_depth, const 
 
 // the batch entry points: planes[m] on the host, or (device_input) in device memory
 static int encode_images_common(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
-                                const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out, bool device_input) {
+                                const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette, uint8_t **blobs_out, size_t *sizes_out,
+                                bool device_input) {
     if (!planes || !blobs_out || !sizes_out || n_images < 1 || w < 1 || h < 1 || nch < 1 || nch > 8 || bit_depth < 1 || bit_depth > 14) return FUIFGPU_E_ARG;
     fuifgpu_encode_options o;
     Lossy l;
-    if (!read_encode_options(opt, o, 1) || !read_lossy_options(lossy, l)) return FUIFGPU_E_ARG;
+    PaletteOpts pal;
+    if (!read_encode_options(opt, o, 1) || !read_lossy_options(lossy, l) || !read_palette_options(palette, nch, pal)) return FUIFGPU_E_ARG;
     if (o.max_properties < 0 || o.max_properties > 2 * kMaxRefs) return FUIFGPU_E_ARG;
     if (o.max_tree_nodes < 1) o.max_tree_nodes = 4095;
     if (o.max_tree_nodes > kMaxNodes) o.max_tree_nodes = kMaxNodes;
@@ -1169,7 +1304,7 @@ static int encode_images_common(const int32_t *const *planes, int n_images, int 
     int rc = FUIFGPU_OK;
     for (int m = 0; m < n_images && rc == FUIFGPU_OK; m++) {
         bool sq = false;
-        rc = build_transformed_image(planes[m], w, h, nch, bit_depth, o, l, imgs[(size_t)m], sq, device_input);
+        rc = build_transformed_image(planes[m], w, h, nch, bit_depth, o, l, pal, imgs[(size_t)m], sq, device_input);
         squeezed[(size_t)m] = sq ? 1 : 0;
     }
     if (rc != FUIFGPU_OK) {   // (the pictures before the failed one may hold device-only channels)
@@ -1182,7 +1317,12 @@ static int encode_images_common(const int32_t *const *planes, int n_images, int 
 }
 extern "C" int fuifgpu_encode_images_lossy(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth,
                                            const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out) {
-    return encode_images_common(planes, n_images, w, h, nch, bit_depth, opt, lossy, blobs_out, sizes_out, false);
+    return encode_images_common(planes, n_images, w, h, nch, bit_depth, opt, lossy, nullptr, blobs_out, sizes_out, false);
+}
+extern "C" int fuifgpu_encode_images_ex(const int32_t *const *planes, int planes_on_device, int n_images, int w, int h, int nch, int bit_depth,
+                                        const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette,
+                                        uint8_t **blobs_out, size_t *sizes_out) {
+    return encode_images_common(planes, n_images, w, h, nch, bit_depth, opt, lossy, palette, blobs_out, sizes_out, planes_on_device != 0);
 }
 extern "C" int fuifgpu_encode_images(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
                                      uint8_t **blobs_out, size_t *sizes_out) {
@@ -1190,5 +1330,5 @@ extern "C" int fuifgpu_encode_images(const int32_t *const *planes, int n_images,
 }
 extern "C" int fuifgpu_encode_images_device(const int32_t *const *planes_device, int n_images, int w, int h, int nch, int bit_depth,
                                             const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out) {
-    return encode_images_common(planes_device, n_images, w, h, nch, bit_depth, opt, lossy, blobs_out, sizes_out, true);
+    return encode_images_common(planes_device, n_images, w, h, nch, bit_depth, opt, lossy, nullptr, blobs_out, sizes_out, true);
 }

@@ -56,6 +56,24 @@ def graphic(w, h, channels=3, bits=8, seed=1, colors=32, step=1):
     return out
 
 
+def from_recipe(recipe):
+    """A picture from a description that fits in a JSON manifest (tests/golden/palette/manifest_palette.json), for inputs that are not one
+    call of the generators above:
+      {"kind": "graphic" | "photographic", "w":, "h":, "channels":, "bits":, "seed":, ...their keywords, "floor_to": k}
+          floor_to: every sample rounded down to a multiple of k (a sparse histogram on a photograph)
+      {"kind": "full", "shape": [c, h, w], "value": v}            one flat value
+      {"kind": "stack", "parts": [recipe, ...]}                     the parts' channels one behind the other (colour + alpha)"""
+    kind = recipe["kind"]
+    if kind == "full":
+        return np.full(tuple(recipe["shape"]), recipe["value"], dtype=np.int32)
+    if kind == "stack":
+        return np.concatenate([from_recipe(p) for p in recipe["parts"]], axis=0)
+    kw = {k: v for k, v in recipe.items() if k not in ("kind", "floor_to")}
+    img = {"graphic": graphic, "photographic": photographic}[kind](**kw)
+    k = recipe.get("floor_to", 1)
+    return (img // k * k).astype(np.int32)
+
+
 def write_pnm(path, planes, maxval=255):
     """planes: (C,H,W) int32 -> P5/P6/P7 file readable by the reference's import/read_pam.h."""
     c, h, w = planes.shape

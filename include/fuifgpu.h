@@ -369,6 +369,43 @@ int fuifgpu_channel_stats(const int32_t *plane_device, int64_t n_samples, int32_
 /* diagnostic: bytes of whole sample planes/channels the LAST encode call of this thread copied host->device and device->host
  * (tables, trees, job records, learner samples, coder state and coded bytes are not planes and are not counted) */
 int fuifgpu_encode_plane_traffic(uint64_t *h2d_bytes, uint64_t *d2h_bytes);
+/* ---- Palette and channel compaction: what the CLI tries by default for PNM input that is not a photograph (fuif.cpp:345-350, 374-430;
+ * transform/palette.h:92-142) ----
+ * In the CLI's order: every channel whose range has 256 values or more and whose samples use fewer than compact_pre_percent of them is
+ * replaced by the ranks of the values that occur (only with opt->ycocg, before YCoCg); after YCoCg one palette of at most palette_colors
+ * colours over all channels, then -- with more than three channels left -- over all but the last; then every channel that uses fewer
+ * than compact_post_percent of its range is compacted.  An attempt that finds too many colours changes nothing and records nothing.
+ * Every success records a Palette transform {first channel, last channel, colours found} and puts its palette (colours x channels,
+ * hshift -1, colours in lexicographic signed order, component 0 most significant) in front of the channel list; palettes are coded
+ * like any channel, with the "left" predictor.  The Squeeze test of fuif.cpp:453 looks at channel 0, i.e. at the newest palette.
+ * A quality below 100 with palette_colors > 0 switches all three off (fuif.cpp:345-350; chroma_quality is not looked at).
+ * With tree_mode 0 the bytes are those of `fuif -I 0 -K .. -X .. -Y ..`.  With opt->gpu_forward, and always for planes on the device, the
+ * colours are collected and the pixels indexed by kernels (fuifgpu_fwd_palette's); the index plane stays on the device like any channel,
+ * and a palette's colours are a table, not a plane: fuifgpu_encode_plane_traffic does not count them. */
+typedef struct {
+    uint32_t struct_size;        /* = sizeof(fuifgpu_palette_options) of the CALLER's header, versioned like fuifgpu_encode_options; fields
+                                    the caller's struct ends before are 0 */
+    int32_t palette_colors;      /* -K: 0 = off, CLI default 256; below 0 or above 32767 (an index is an int16 sample), or above 0 for
+                                    pictures of more than four channels, is FUIFGPU_E_ARG */
+    float compact_post_percent;  /* -X: 0 = off, CLI default 70; NaN, negative or above 100 is FUIFGPU_E_ARG */
+    float compact_pre_percent;   /* -Y: likewise */
+} fuifgpu_palette_options;
+/* fuifgpu_encode_image_lossy / fuifgpu_encode_images_lossy / fuifgpu_encode_images_device (planes_on_device != 0) with the three options.
+ * palette == NULL or all three 0 writes exactly the bytes of those calls.  Pictures of one batch may end up with different transform
+ * chains and channel counts.  Found by symbol lookup: the ABI version does not change. */
+int fuifgpu_encode_image_ex(const int32_t *planes, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
+                            const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette, uint8_t **blob_out, size_t *size_out);
+int fuifgpu_encode_images_ex(const int32_t *const *planes, int planes_on_device, int n_images, int w, int h, int nch, int bit_depth,
+                             const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette,
+                             uint8_t **blobs_out, size_t *sizes_out);
+/* transform/palette.h:92-142 on raw device planes: the distinct tuples of planes_device[0..nb-1] (nb 1..4, n_samples int32 each, values
+ * of int16 range) are collected on the GPU.  More than max_colors of them: *n_colors = -1, nothing else is written.  Otherwise *n_colors
+ * is their number, palette_host[c * max_colors + k] component c of colour k (host memory, nb * max_colors words, colours in the
+ * reference's order) and index_device[i] the colour of sample i (device memory; it may be planes_device[0] itself).  Synchronous; the
+ * kernels run on `stream`.  nb outside 1..4, a negative count, a sample outside the int16 range, or a NULL pointer with work to do:
+ * FUIFGPU_E_ARG. */
+int fuifgpu_fwd_palette(const int32_t *const *planes_device, int nb, int64_t n_samples, int max_colors, int32_t *index_device,
+                        int32_t *palette_host, int *n_colors, void *stream);
 /* host: the constant fuif.cpp:459-503 gives one channel -- squeeze_option = opt->squeeze (the OPTION, not whether the picture was large
  * enough to be squeezed), chroma_table = 1 for the chroma table, shift = hcshift + vcshift (capped at 15).  1 when both qualities are
  * >= 100.  A negative shift or a quality the entry points above refuse gives -FUIFGPU_E_ARG. */
