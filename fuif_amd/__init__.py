@@ -109,6 +109,21 @@ def make_palette_options(palette_colors=0, compact_post=0.0, compact_pre=0.0):
     return PaletteOptions(C.sizeof(PaletteOptions), int(palette_colors), float(compact_post), float(compact_pre))
 
 
+class AnimationOptions(C.Structure):
+    """fuifgpu_animation_options (include/fuifgpu.h): the frames of `fuif frame-%02d.ppm`, `-F framerate` and `-M -1` / `-M 0`"""
+    _fields_ = [("struct_size", C.c_uint32), ("nb_frames", C.c_int32), ("framerate", C.c_int32), ("match_previous", C.c_int32)]
+
+
+def make_animation_options(nb_frames, framerate=None, match_previous=True):
+    """AnimationOptions for the keywords of encode_animation / encode_animations / encode_animations_device.  match_previous: True / False
+    (or 1 / 0); any other number goes to the library as it is, which refuses it (deeper distances are not offered)"""
+    if framerate is None:
+        framerate = 0
+    elif not np.isfinite(framerate) or framerate < 0 or framerate != int(framerate):
+        raise FuifGpuError(4, "encode_animation: the frame rate is a whole number of frames per second, 1 or more (None = the CLI's 10)")
+    return AnimationOptions(C.sizeof(AnimationOptions), int(nb_frames), int(framerate), int(match_previous))
+
+
 def make_lossy_options(quality=None, chroma_quality=None):
     """LossyOptions for the two keywords of encode_image / encode_images: a missing quality is 100 (lossless luma), a missing
     chroma quality "same as quality" (the CLI's default, 101)"""
@@ -135,6 +150,7 @@ ABI_SYMBOLS = [
     "fuifgpu_encode_image_lossy", "fuifgpu_encode_images_lossy", "fuifgpu_quantization_constant",
     "fuifgpu_encode_images_device", "fuifgpu_channel_stats", "fuifgpu_encode_plane_traffic",
     "fuifgpu_encode_image_ex", "fuifgpu_encode_images_ex", "fuifgpu_fwd_palette",
+    "fuifgpu_encode_animation", "fuifgpu_encode_animations", "fuifgpu_fwd_match_frames",
     "fuifgpu_plane_checksums", "fuifgpu_device_count", "fuifgpu_set_device", "fuifgpu_get_device", "fuifgpu_batch_device", "fuifgpu_peer_copy", "fuifgpu_batch_set_in_flight",
 ]
 
@@ -240,6 +256,9 @@ def lib():
     L.fuifgpu_encode_image_ex.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(PaletteOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.fuifgpu_encode_images_ex.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(PaletteOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.fuifgpu_fwd_palette.argtypes = [C.POINTER(vp), C.c_int, C.c_int64, C.c_int, vp, vp, C.POINTER(C.c_int), vp]
+    L.fuifgpu_encode_animation.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(PaletteOptions), C.POINTER(AnimationOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.fuifgpu_encode_animations.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(PaletteOptions), C.POINTER(AnimationOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.fuifgpu_fwd_match_frames.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     L.fuifgpu_encode_plane_traffic.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.fuifgpu_quantization_constant.argtypes = [C.c_float, C.c_float, C.c_int, C.c_int, C.c_int]
     L.fuifgpu_encode_image.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
@@ -603,6 +622,95 @@ def encode_images_device(planes, w=None, h=None, nch=None, bit_depth=8, ycocg=Tr
         blobs.append(C.string_at(outs[k], sizes[k]))
         lib().fuifgpu_free_blob(C.c_void_p(outs[k]))
     return blobs
+
+
+def _encode_options_from_keywords(gpu_forward, gpu_entropy, bit_depth=8, ycocg=True, squeeze=True, max_properties=12, tree_mode=1, max_tree_nodes=4095,
+                                  index=False, split_bits=None, quality=None, chroma_quality=None, palette_colors=0, compact_post=0.0, compact_pre=0.0):
+    """the keywords encode_image has besides the two routes -> (bit_depth, EncodeOptions, LossyOptions or None, PaletteOptions or None)"""
+    split_bits = DEFAULT_SPLIT_BITS if split_bits is None else split_bits
+    opt = make_encode_options(int(ycocg), int(squeeze), max_properties, tree_mode, max_tree_nodes, int(index), int(split_bits), int(gpu_forward), int(gpu_entropy))
+    lossy = None if quality is None and chroma_quality is None else make_lossy_options(quality, chroma_quality)
+    return bit_depth, opt, lossy, make_palette_options(palette_colors, compact_post, compact_pre)
+
+
+def _byref_or_none(struct):
+    return None if struct is None else C.byref(struct)
+
+
+def _take_blobs(outs, sizes, n):
+    blobs = []
+    for k in range(n):
+        blobs.append(C.string_at(outs[k], sizes[k]))
+        lib().fuifgpu_free_blob(C.c_void_p(outs[k]))
+    return blobs
+
+
+def encode_animation(frames, framerate=None, match_previous=True, gpu_forward=False, gpu_entropy=False, **keywords):
+    """(F,C,H,W) int32 frames -> the bytes `fuif frame-%02d.ppm out.fuif` writes for them: one strip under the magic FUAF and, with
+    match_previous (the CLI's `-M -1`; False = `-M 0`), the Matching transform against the frame above (fuifgpu_encode_animation).
+    framerate: `-F` (None = 10).  The other keywords are encode_image's.  One frame writes what encode_image writes."""
+    frames = np.ascontiguousarray(frames, dtype=np.int32)
+    if frames.ndim != 4:
+        raise FuifGpuError(4, "encode_animation: frames of shape (F, C, H, W)")
+    f, c, h, w = frames.shape
+    bit_depth, opt, lossy, pal = _encode_options_from_keywords(gpu_forward, gpu_entropy, **keywords)
+    anim = make_animation_options(f, framerate, match_previous)
+    out, n = C.c_void_p(), C.c_size_t(0)
+    _check(lib().fuifgpu_encode_animation(frames.ctypes.data, w, h, c, bit_depth, C.byref(opt), _byref_or_none(lossy), _byref_or_none(pal), C.byref(anim),
+                                          C.byref(out), C.byref(n)))
+    blob = C.string_at(out.value, n.value)
+    lib().fuifgpu_free_blob(out)
+    return blob
+
+
+def encode_animations(clips, framerate=None, match_previous=True, gpu_forward=False, **keywords):
+    """a batch of equally shaped (F,C,H,W) clips -> list of byte strings, what encode_animation writes for each; the pixel loops of all
+    their channel groups run in one launch pair (fuifgpu_encode_animations, the batch writer of encode_images)"""
+    arrs = [np.ascontiguousarray(cl, dtype=np.int32) for cl in clips]
+    if not arrs or arrs[0].ndim != 4 or any(a.shape != arrs[0].shape for a in arrs):
+        raise FuifGpuError(4, "encode_animations: all clips of a batch have one shape (F, C, H, W)")
+    f, c, h, w = arrs[0].shape
+    n = len(arrs)
+    bit_depth, opt, lossy, pal = _encode_options_from_keywords(gpu_forward, 1, **keywords)
+    anim = make_animation_options(f, framerate, match_previous)
+    ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
+    outs, sizes = (C.c_void_p * n)(), (C.c_size_t * n)()
+    _check(lib().fuifgpu_encode_animations(ptrs, 0, n, w, h, c, bit_depth, C.byref(opt), _byref_or_none(lossy), _byref_or_none(pal), C.byref(anim), outs, sizes))
+    return _take_blobs(outs, sizes, n)
+
+
+def encode_animations_device(clips, nb_frames=None, w=None, h=None, nch=None, framerate=None, match_previous=True, **keywords):
+    """clips that already live in DEVICE memory -> list of byte strings, the bytes encode_animations writes for the same samples.  The
+    frames are read, never written; no channel and no match channel crosses to the host unless its group is rolled back to
+    "uncompressed" (encode_plane_traffic).  clips: a list of integer device pointers (each nb_frames x nch planes of w*h int32, frame
+    after frame; nb_frames, w, h, nch given), or an object with data_ptr(), shape == (N, F, C, H, W), an int32 dtype and contiguous layout"""
+    if hasattr(clips, "data_ptr"):
+        shape = tuple(int(v) for v in clips.shape)
+        if len(shape) != 5 or "int32" not in str(clips.dtype) or (hasattr(clips, "is_contiguous") and not clips.is_contiguous()):
+            raise FuifGpuError(4, "encode_animations_device: a tensor must be contiguous int32 of shape (N, F, C, H, W)")
+        n, nb_frames, nch, h, w = shape
+        ptrs = [clips.data_ptr() + 4 * k * nb_frames * nch * h * w for k in range(n)]
+    else:
+        ptrs = [int(p) if p else 0 for p in clips]
+        if nb_frames is None or w is None or h is None or nch is None:
+            raise FuifGpuError(4, "encode_animations_device: nb_frames, w, h and nch go with a list of device pointers")
+    n = len(ptrs)
+    bit_depth, opt, lossy, pal = _encode_options_from_keywords(1, 1, **keywords)
+    anim = make_animation_options(nb_frames, framerate, match_previous)
+    arr = (C.c_void_p * max(n, 1))(*ptrs)
+    outs, sizes = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+    _check(lib().fuifgpu_encode_animations(arr, 1, n, int(w), int(h), int(nch), bit_depth, C.byref(opt), _byref_or_none(lossy), _byref_or_none(pal), C.byref(anim),
+                                           outs, sizes))
+    return _take_blobs(outs, sizes, n)
+
+
+def fwd_match_frames(plane_device_ptrs, w, h, nb_frames, match_device_ptr, stream=None):
+    """fuifgpu_fwd_match_frames: the forward Matching against the previous frame (transform/2dmatch.h:303-381, distance -1) of up to eight
+    planes of a w x h strip of nb_frames frames in DEVICE memory: the match channel goes to match_device_ptr (w*h int32) and the matched
+    samples of the planes become 0 IN PLACE; asynchronous on `stream`"""
+    nb = len(plane_device_ptrs)
+    ptrs = (C.c_void_p * max(nb, 1))(*[int(p) if p else 0 for p in plane_device_ptrs])
+    _check(lib().fuifgpu_fwd_match_frames(ptrs, nb, int(w), int(h), int(nb_frames), match_device_ptr, stream))
 
 
 def channel_stats(plane_device_ptr, n_samples, stats_device_ptr, stream=None):

@@ -286,6 +286,7 @@ int dev_copy(void *dst_device, const void *src_device, size_t bytes) {
     if (bytes) HIPCHK(hipMemcpy(dst_device, src_device, bytes, hipMemcpyDeviceToDevice));
     return FUIFGPU_OK;
 }
+int fail_with_message(int code, const char *what) { return fail_msg(code, what); }
 }  // namespace fuifgpu
 
 extern "C" {
@@ -1219,6 +1220,15 @@ int fuifgpu_fwd_palette(const int32_t *const *planes_device, int nb, int64_t n_s
     const int rc = fwd_palette_gpu(planes_device, nb, n_samples, max_colors, index_device, rows, n_colors, stream);
     if (rc != FUIFGPU_OK || *n_colors <= 0) return rc;
     for (int c = 0; c < nb; c++) memcpy(palette_host + (size_t)c * max_colors, rows.data() + (size_t)c * *n_colors, sizeof(int32_t) * (size_t)*n_colors);
+    return FUIFGPU_OK;
+}
+int fuifgpu_fwd_match_frames(const int32_t *const *planes_dev, int n_planes, int w, int h, int nb_frames, int32_t *match_dev, void *stream) {
+    if (!planes_dev || !match_dev || n_planes < 1 || n_planes > 8 || w < 1 || h < 1 || nb_frames < 2 || h % nb_frames || (int64_t)w * h > INT32_MAX) return FUIFGPU_E_ARG;
+    MatchPlanes mp{};
+    mp.nb = n_planes;
+    for (int c = 0; c < n_planes; c++) { if (!planes_dev[c]) return FUIFGPU_E_ARG; mp.p[c] = const_cast<int32_t *>(planes_dev[c]); }
+    launch_fwd_match_frames(mp, w, h, h / nb_frames, 1, 0, match_dev, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
     return FUIFGPU_OK;
 }
 // a plane anywhere in device memory as an element offset from a null base (every plane pointer is 4-byte aligned)

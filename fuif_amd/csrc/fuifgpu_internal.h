@@ -191,6 +191,8 @@ int fwd_palette_gpu(const int32_t *const *planes_device, int nb, int64_t n, int 
                     int *n_colors, void *stream = nullptr);
 // device -> device copy on the null stream (the writer's working copies of caller-owned planes)
 int dev_copy(void *dst_device, const void *src_device, size_t bytes);
+// `code`, with `what` as the calling thread's fuifgpu_last_error (capi.hip)
+int fail_with_message(int code, const char *what);
 
 // One channel group of a stream: where its header starts and the first channel it codes (index.cpp)
 struct GroupEntry {

@@ -72,7 +72,9 @@ DEV int enc_props_and_guess(const EncGroup &g, int64_t i, int32_t *p) {
     for (int k = 0; k < g.nrefs; k++) {   // context_predict.h:233-289, one pixel
         const EncRef rc = g.refs[k];
         int ry = (y << g.vshift) >> rc.vshift; if (ry >= rc.h) ry = rc.h - 1;
-        int rx = (x << g.hshift) >> rc.hshift; if (rx >= rc.w) rx = rc.w - 1;
+        // a palette (hshift -1) coded behind an ordinary meta-channel (the match channel of an animation): the reference's step size is
+        // (1 << rc.hshift) >> -1, 0 on its x86 build, and every sample reads the reference row's LAST sample (k_maniac_decode does the same)
+        int rx = g.hshift < 0 ? rc.w - 1 : (x << g.hshift) >> rc.hshift; if (rx >= rc.w) rx = rc.w - 1;
         const int v = rc.data[(int64_t)ry * rc.w + rx];
         p[o++] = e_iabs(v); p[o++] = e_slog(v);
     }

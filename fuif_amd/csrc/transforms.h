@@ -61,5 +61,13 @@ void launch_palette_index(const PalettePlanes &pp, int64_t n, const unsigned lon
                           int32_t *index, hipStream_t stream);
 void launch_palette_collect1(const int32_t *plane, int64_t n, uint32_t *dev_bitmap, uint32_t *dev_ctl, hipStream_t stream);
 void launch_palette_index1(const int32_t *plane, int64_t n, const uint32_t *dev_bitmap, const int32_t *dev_prefix, int32_t *index, hipStream_t stream);
+// forward Matching against the previous frame (transform/2dmatch.h:303-381 with maxdist = -1) of a strip of frames fh rows high: the
+// match channel (w x h, every sample written) from the planes, the erode, then the matched samples of every plane set to zero in place.
+// Three launches; picture z of n_pictures has its planes and its match channel z * pic_stride samples behind picture 0's
+struct MatchPlanes {
+    int32_t *p[8];
+    int32_t nb;
+};
+void launch_fwd_match_frames(const MatchPlanes &mp, int w, int h, int fh, int n_pictures, int64_t pic_stride, int32_t *match, hipStream_t stream);
 
 }  // namespace fuifgpu

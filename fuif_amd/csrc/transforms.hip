@@ -1218,6 +1218,87 @@ void launch_palette_index1(const int32_t *plane, int64_t n, const uint32_t *dev_
     if (n <= 0) return;
     hipLaunchKernelGGL(k_palette_index1, dim3(palette_blocks(n)), dim3(256), 0, stream, plane, n, dev_bitmap, dev_prefix, index);
 }
+// ---------------------------------------------------------------------------------------------
+// Forward Matching against the previous frame (transform/2dmatch.h:303-381 with maxdist = -1: what the CLI does for an animation).
+// The strip is nb_frames pictures of w x fh one above the other; a sample of row y >= fh "equals" when every plane holds what it holds
+// fh rows up.  The reference walks each row with a counter and back-fills (2dmatch.h:314-335): what comes out is m = 1 on every maximal
+// horizontal run of equal samples that is at least minmatch long.  Here one wavefront takes one row, 64 samples at a time: the ballot of
+// "equals" is the chunk's mask, a lane finds the unequal sample below and above itself in it, `carry` brings the run that ends in front
+// of the chunk (saturated at 64: minmatch <= 40) and the mask of the NEXT chunk, taken one iteration ahead, the run that goes on behind
+// it -- a run that crosses a whole chunk is long enough whatever follows.  Rows of frame 0 are written 0, so the kernel defines every
+// sample of m; a row narrower than minmatch gets zeros.  Every loop runs ceil(w / 64) times for all 64 lanes (the ballots are uniform).
+__global__ __launch_bounds__(64) void k_match_frames_runs(MatchPlanes mp, int w, int fh, int minmatch, int64_t pic_stride, int32_t *match) {
+    const int y = blockIdx.x, lane = threadIdx.x;
+    const int64_t pic = (int64_t)blockIdx.z * pic_stride, row = pic + (int64_t)y * w, up = row - (int64_t)fh * w;
+    if (y < fh) {
+        for (int x = lane; x < w; x += 64) match[row + x] = 0;
+        return;
+    }
+    auto equal_at = [&](int x) {
+        if (x >= w) return false;
+        bool eq = true;
+        for (int c = 0; c < mp.nb; c++) eq &= mp.p[c][row + x] == mp.p[c][up + x];
+        return eq;
+    };
+    unsigned long long cur = __ballot(equal_at(lane));
+    int carry = 0;
+    for (int x0 = 0; x0 < w; x0 += 64) {
+        const unsigned long long next = __ballot(equal_at(x0 + 64 + lane));
+        const unsigned long long differ = ~cur;
+        bool long_enough = false;
+        if ((cur >> lane) & 1ull) {
+            const unsigned long long below = differ & ((1ull << lane) - 1ull);
+            const int left = below ? lane - 64 + __builtin_clzll(below) : lane + carry;            // equal samples in front of this one
+            const unsigned long long above = lane < 63 ? differ >> (lane + 1) : 0ull;
+            const int right = above ? __builtin_ctzll(above) : 63 - lane + (~next ? __builtin_ctzll(~next) : 64);   // ... and behind it
+            long_enough = left + 1 + right >= minmatch;
+        }
+        if (x0 + lane < w) match[row + x0 + lane] = long_enough ? 1 : 0;
+        carry = differ ? __builtin_clzll(differ) : 64;
+        cur = next;
+    }
+}
+// The three erode sweeps of 2dmatch.h:355-369.  The reference sweeps in place in raster order and flags (negates) a matched sample when
+// the sample above or to its left is 0 -- those were visited before it, so 0 there means "never matched", whatever the sweep -- or when
+// the sample below or to its right is <= 0 -- not visited yet, so: never matched, or flagged by an EARLIER sweep.  The picture's bottom,
+// left and right edges do not count; the row above frame 1 is frame 0's last, all zero.  So sweep k flags what sweep k-1 flagged plus the
+// matched samples whose matched lower or right neighbour sweep k-1 flagged, and three sweeps are this depth-3 recursion over the
+// match channel AS k_match_frames_runs LEFT IT.  The kernel works in place: it only ever asks "is this sample 0", and a flag turns 1
+// into -1, never into 0, so a neighbour that another lane has flagged already answers as it did before.
+template <int SWEEPS>
+DEV bool match_flagged(const int32_t *m, int w, int h, int x, int y) {   // (x, y) is matched
+    const int64_t i = (int64_t)y * w + x;
+    if constexpr (SWEEPS == 1) {
+        return m[i - w] == 0 || (x > 0 && m[i - 1] == 0) || (y + 1 < h && m[i + w] == 0) || (x + 1 < w && m[i + 1] == 0);
+    } else {
+        return match_flagged<SWEEPS - 1>(m, w, h, x, y) || (y + 1 < h && m[i + w] != 0 && match_flagged<SWEEPS - 1>(m, w, h, x, y + 1)) ||
+               (x + 1 < w && m[i + 1] != 0 && match_flagged<SWEEPS - 1>(m, w, h, x + 1, y));
+    }
+}
+__global__ __launch_bounds__(256) void k_match_frames_erode(int w, int h, int fh, int64_t pic_stride, int32_t *match) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (int64_t)fh * w || i >= (int64_t)w * h) return;
+    int32_t *m = match + (int64_t)blockIdx.z * pic_stride;
+    if (m[i] != 0 && match_flagged<3>(m, w, h, (int)(i % w), (int)(i / w))) m[i] = -1;
+}
+// 2dmatch.h:372-379: a matched sample that kept its mark is 0 in every plane (the decoder copies it from the frame above), a flagged one
+// keeps its samples and is an ordinary 1 in the match channel again
+__global__ __launch_bounds__(256) void k_match_frames_apply(MatchPlanes mp, int w, int h, int fh, int64_t pic_stride, int32_t *match) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (int64_t)fh * w || i >= (int64_t)w * h) return;
+    const int64_t at = (int64_t)blockIdx.z * pic_stride + i;
+    const int32_t v = match[at];
+    if (v > 0) for (int c = 0; c < mp.nb; c++) mp.p[c][at] = 0;
+    else if (v < 0) match[at] = 1;
+}
+void launch_fwd_match_frames(const MatchPlanes &mp, int w, int h, int fh, int n_pictures, int64_t pic_stride, int32_t *match, hipStream_t stream) {
+    if (w < 1 || h < 1 || n_pictures < 1) return;
+    const int minmatch = std::max(5, std::min(40, w / 50));   // 2dmatch.h:312
+    const unsigned blocks = (unsigned)(((int64_t)w * h + 255) / 256);
+    hipLaunchKernelGGL(k_match_frames_runs, dim3((unsigned)h, 1, (unsigned)n_pictures), dim3(64), 0, stream, mp, w, fh, minmatch, pic_stride, match);
+    hipLaunchKernelGGL(k_match_frames_erode, dim3(blocks, 1, (unsigned)n_pictures), dim3(256), 0, stream, w, h, fh, pic_stride, match);
+    hipLaunchKernelGGL(k_match_frames_apply, dim3(blocks, 1, (unsigned)n_pictures), dim3(256), 0, stream, mp, w, h, fh, pic_stride, match);
+}
 void launch_fwd_ycocg(int32_t *c0, int32_t *c1, int32_t *c2, int64_t n, hipStream_t stream) {
     hipLaunchKernelGGL(k_fwd_ycocg,dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, c0, c1, c2, n);
 }

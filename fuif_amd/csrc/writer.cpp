@@ -24,6 +24,11 @@
 // three integers per channel (k_channel_stats) and the learner's samples (k_learn_samples_jobs), and writes the same bytes.
 // With a palette the colours are collected and the pixels indexed there too (k_palette_collect / k_palette_index): the index plane stays on
 // the device like any channel; the palette itself is a table the host sorts, not a plane, and fuifgpu_encode_plane_traffic does not count it.
+// Animations (fuifgpu_encode_animation, `fuif frame-%02d.ppm out.fuif`): the frames are one strip under the magic FUAF (encoding.cpp:458-473)
+// and, by default, Matching against the previous frame runs between the palettes and Squeeze (fuif.cpp:440-448; transform/2dmatch.h:303-381
+// with maxdist = -1); on the GPU routes k_match_frames_runs / _erode / _apply do it.  Only that distance and "off" are offered: from the
+// second distance on the reference's back-fill (2dmatch.h:327-329) counts positions, not unmatched samples, and overwrites samples an
+// earlier distance matched with an offset that was never compared -- a lossless mode that loses pixels, which is not reproduced.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -175,6 +180,7 @@ struct Range { int lo, hi; };
 struct Image {
     std::vector<Chan> ch;
     int w = 0, h = 0, maxval = 0, nb_channels = 0, nb_meta = 0;
+    int nb_frames = 1, den = 10;   // an animation: h = nb_frames frames one above the other; den: frames per second (image.h `den`)
     std::vector<TransformDesc> transforms;
     int downscales[6];
 };
@@ -405,6 +411,67 @@ int compact_channels(Image &img, float fraction, bool pre, bool on_gpu) {
     return rc;
 }
 
+// ---- animations: forward Matching against the previous frame (transform/2dmatch.h:245-262, 303-381 with maxdist = -1) -------------
+struct AnimOpts {
+    int nb_frames = 1, den = 10;
+    bool match = true;
+};
+// the host's form is the reference's loop nest as it stands, in-place erode included (the kernels' data-parallel form is checked against it)
+void fwd_match_frames_host(Chan *chans, int nb, int fh, Chan &m) {
+    const int w = m.w, h = m.h;
+    const int minmatchcount = std::max(5, std::min(40, w / 50));
+    auto M = [&](int y, int x) -> int32_t & { return m.data[(size_t)y * w + x]; };
+    for (int y = fh; y < h; y++) {
+        int matchcount = 0;
+        bool firstmatch = true;
+        for (int x = 0; x < w; x++) {
+            bool nomatch = false;
+            for (int c = 0; c < nb; c++) nomatch |= chans[c].data[(size_t)y * w + x] != chans[c].data[(size_t)(y - fh) * w + x];
+            if (nomatch) { matchcount = 0; firstmatch = true; continue; }
+            matchcount++;
+            if (matchcount >= minmatchcount) {
+                if (firstmatch) for (int prev_x = x - matchcount + 1; prev_x < x; prev_x++) M(y, prev_x) = 1;
+                firstmatch = false;
+                M(y, x) = 1;
+            }
+        }
+    }
+    for (int it = 0; it < 3; it++)   // 2dmatch.h:355-369
+        for (int y = fh; y < h; y++)
+            for (int x = 0; x < w; x++)
+                if (M(y, x) > 0 && (M(y - 1, x) == 0 || (x > 0 && M(y, x - 1) == 0) || (y + 1 < h && M(y + 1, x) <= 0) || (x + 1 < w && M(y, x + 1) <= 0)))
+                    M(y, x) = -M(y, x);
+    for (int y = fh; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            if (M(y, x) > 0) for (int c = 0; c < nb; c++) chans[c].data[(size_t)y * w + x] = 0;
+            else if (M(y, x) < 0) M(y, x) *= -1;
+        }
+}
+// Image::do_transform of the Matching: the meta-channel goes in FRONT of the channel list (meta_match, 2dmatch.h:191-193), the transform is
+// recorded without parameters (:256: channels 0..nb_channels-1, no soft match)
+int fwd_match_frames(Image &img, bool on_gpu) {
+    const int bc = img.nb_meta, nb = img.nb_channels;
+    if (nb > 8) return FUIFGPU_E_ARG;
+    Chan m;   // Channel mch(w, h, 0, 1)
+    m.w = img.ch[bc].w; m.h = img.ch[bc].h; m.minval = 0; m.maxval = 1;
+    const int fh = m.h / img.nb_frames;
+    m.q = 2 * fh * fh + (fh & 1);   // the code of the offset "exactly one frame up" (:310)
+    int rc = FUIFGPU_OK;
+    if (on_gpu) {
+        const int32_t *planes[8];
+        for (int c = 0; c < nb; c++) planes[c] = img.ch[bc + c].dev;
+        m.dev = (int32_t *)fuifgpu_dev_alloc(sizeof(int32_t) * (size_t)m.w * m.h);
+        rc = m.dev ? fuifgpu_fwd_match_frames(planes, nb, m.w, m.h, img.nb_frames, m.dev, nullptr) : FUIFGPU_E_HIP;
+    } else {
+        m.data.assign((size_t)m.w * m.h, 0);
+        fwd_match_frames_host(&img.ch[bc], nb, fh, m);
+    }
+    img.ch.insert(img.ch.begin(), std::move(m));
+    img.nb_meta++;
+    img.transforms.push_back({TR_2DMATCH, {}});
+    return rc;
+}
+
 // ---- lossy: the CLI's quantisation constants for Squeeze channels (fuif.cpp:459-503) ---------------------------------------------
 // Everything below is float arithmetic whose roundings decide an integer: the variables are floats initialised from double literals,
 // the quality mapping is evaluated in double and stored to float, the products run left to right in float (no contraction: the
@@ -517,7 +584,9 @@ inline int props_and_guess(int32_t *p, const Chan &c, const std::vector<RefInfo>
     for (const RefInfo &r : refs) {
         const Chan &rc = *r.c;
         int ry = (y << c.vshift) >> rc.vshift; if (ry >= rc.h) ry = rc.h - 1;
-        int rx = (x << c.hshift) >> rc.hshift; if (rx >= rc.w) rx = rc.w - 1;
+        // a palette (hshift -1) coded behind the match channel: the reference's step size is (1 << rc.hshift) >> -1, 0 on its x86 build,
+        // and every sample reads the reference row's last sample (context_predict.h:248-276)
+        int rx = c.hshift < 0 ? rc.w - 1 : (x << c.hshift) >> rc.hshift; if (rx >= rc.w) rx = rc.w - 1;
         int v = rc.data[(size_t)ry * rc.w + rx];
         p[o++] = iabs(v); p[o++] = slog(v);
     }
@@ -854,16 +923,27 @@ int write_stream(Image &img, int nch, int bit_depth, bool squeezed, const fuifgp
 // planes -> Image with the CLI's default forward transforms applied (fuif.cpp:380-455) and, with a quality, its Quantize (fuif.cpp:459-503),
 // on the host or on the GPU.  device_input: `planes` is device memory -- the forward transforms run on working copies there (gpu_forward is
 // implied) and the transformed channels STAY there, device-only (Chan::resident), for write_streams_batch
-static int build_transformed_image(const int32_t *planes, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options &o,
-                                   const fuifgpu::Lossy &lossy, fuifgpu::PaletteOpts pal, fuifgpu::Image &img, bool &squeezed, bool device_input = false) {
+// An animation (anim.nb_frames > 1): `planes` holds the frames one after the other, each nch planes of w x frame_h; channel c of the strip
+// is plane c of every frame, one above the other (fuif.cpp:319-327)
+static int build_transformed_image(const int32_t *planes, int w, int frame_h, int nch, int bit_depth, const fuifgpu_encode_options &o,
+                                   const fuifgpu::Lossy &lossy, fuifgpu::PaletteOpts pal, const fuifgpu::AnimOpts &anim, fuifgpu::Image &img, bool &squeezed,
+                                   bool device_input = false) {
     using namespace fuifgpu;
     if (lossy.quality < 100.f && pal.colors > 0) pal = PaletteOpts();   // fuif.cpp:345-350: `quality` alone is read, and only -K > 0 clears the other two
+    const int h = frame_h * anim.nb_frames;
+    const size_t frame_samples = (size_t)w * frame_h;
     img.w = w; img.h = h; img.maxval = (1 << bit_depth) - 1; img.nb_channels = nch;
+    img.nb_frames = anim.nb_frames; img.den = anim.den;
     img.ch.resize(nch);
     for (int c = 0; c < nch; c++) {
         Chan &ch = img.ch[c];
         ch.w = w; ch.h = h; ch.component = c; ch.minval = 0; ch.maxval = img.maxval;
-        if (!device_input) ch.data.assign(planes + (size_t)c * w * h, planes + (size_t)(c + 1) * w * h);
+        if (device_input) continue;
+        ch.data.reserve((size_t)w * h);
+        for (int f = 0; f < anim.nb_frames; f++) {
+            const int32_t *src = planes + ((size_t)f * nch + c) * frame_samples;
+            ch.data.insert(ch.data.end(), src, src + frame_samples);
+        }
     }
     const bool on_gpu = o.gpu_forward != 0 || device_input;
     int rc = FUIFGPU_OK;
@@ -873,7 +953,9 @@ static int build_transformed_image(const int32_t *planes, int w, int h, int nch,
             Chan &ch = img.ch[c];
             ch.dev = (int32_t *)fuifgpu_dev_alloc(sizeof(int32_t) * (size_t)w * h);
             if (!ch.dev) rc = FUIFGPU_E_HIP;
-            else if (device_input) rc = dev_copy(ch.dev, planes + (size_t)c * w * h, sizeof(int32_t) * (size_t)w * h);   // the caller's planes are never written
+            else if (device_input)   // the caller's planes are never written
+                for (int f = 0; f < anim.nb_frames && rc == FUIFGPU_OK; f++)
+                    rc = dev_copy(ch.dev + (size_t)f * frame_samples, planes + ((size_t)f * nch + c) * frame_samples, sizeof(int32_t) * frame_samples);
             else rc = plane_upload(ch.dev, ch.data.data(), (size_t)w * h);
             ch.data.clear();
         }
@@ -890,8 +972,9 @@ static int build_transformed_image(const int32_t *planes, int w, int h, int nch,
         if (rc == FUIFGPU_OK && img.nb_channels > 3) rc = try_palette(img, 0, img.nb_channels - 2, pal.colors, on_gpu);
     }
     if (rc == FUIFGPU_OK && pal.post > 0.f) rc = compact_channels(img, pal.post, false, on_gpu);   // fuif.cpp:418-430
+    if (rc == FUIFGPU_OK && anim.nb_frames > 1 && anim.match) rc = fwd_match_frames(img, on_gpu);   // fuif.cpp:440-448
     squeezed = false;
-    if (rc == FUIFGPU_OK && o.squeeze && (int64_t)img.ch[0].w * img.ch[0].h > 20) {  // fuif.cpp:453: channel[0] -- a palette, once there is one
+    if (rc == FUIFGPU_OK && o.squeeze && (int64_t)img.ch[0].w * img.ch[0].h > 20) {  // fuif.cpp:453: channel[0] -- the match channel or a palette, once there is one
         std::vector<int> params = default_squeeze_params(img);
         rc = fwd_squeeze(img, params, on_gpu);
         img.transforms.push_back({TR_SQUEEZE, {}});  // empty parameter list = "default" in the stream
@@ -958,6 +1041,27 @@ static bool read_palette_options(const fuifgpu_palette_options *palette, int nch
     return true;
 }
 
+// fuifgpu_animation_options: NULL = one frame; the strip must fit the format (h an int, a channel at most 2^31-1 samples) and the offset
+// code 2*fh*fh + 1 an int
+static int read_animation_options(const fuifgpu_animation_options *anim, int w, int frame_h, AnimOpts &a) {
+    a = AnimOpts();
+    if (anim) {
+        if (anim->struct_size < sizeof(fuifgpu_animation_options) || (anim->struct_size & 3u)) return FUIFGPU_E_ARG;
+        if (anim->nb_frames < 1) return fail_with_message(FUIFGPU_E_ARG, "encode_animation: an animation has at least one frame");
+        if (anim->framerate < 0) return fail_with_message(FUIFGPU_E_ARG, "encode_animation: a negative frame rate");
+        if (anim->match_previous != 0 && anim->match_previous != 1)
+            return fail_with_message(FUIFGPU_E_ARG, "encode_animation: match_previous is 1 (fuif -M -1, the previous frame) or 0 (-M 0); deeper distances are not "
+                                                    "offered: the reference's back-fill overwrites samples an earlier distance matched with an offset it never compared");
+        a.nb_frames = anim->nb_frames;
+        a.den = anim->framerate > 0 ? anim->framerate : 10;   // fuif.cpp:335; image.h: den = 10
+        a.match = anim->match_previous != 0;
+    }
+    if (w < 1 || frame_h < 1) return FUIFGPU_E_ARG;
+    if ((int64_t)frame_h * a.nb_frames * w > INT32_MAX || (a.nb_frames > 1 && frame_h > 32767))
+        return fail_with_message(FUIFGPU_E_ARG, "encode_animation: the strip of frames is higher than the format's h holds");
+    return FUIFGPU_OK;
+}
+
 int fuifgpu_encode_plane_traffic(uint64_t *h2d_bytes, uint64_t *d2h_bytes) {
     if (h2d_bytes) *h2d_bytes = g_plane_h2d;
     if (d2h_bytes) *d2h_bytes = g_plane_d2h;
@@ -971,13 +1075,16 @@ int fuifgpu_quantization_constant(float quality, float chroma_quality, int squee
 }
 
 // planes: nch planes of w*h int32 in [0, 2^bit_depth-1].
-int fuifgpu_encode_image_ex(const int32_t *planes, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
-                            const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette, uint8_t **blob_out, size_t *size_out) {
+int fuifgpu_encode_animation(const int32_t *planes, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
+                             const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette, const fuifgpu_animation_options *anim_options,
+                             uint8_t **blob_out, size_t *size_out) {
     if (!planes || !blob_out || !size_out || w < 1 || h < 1 || nch < 1 || nch > 8 || bit_depth < 1 || bit_depth > 14) return FUIFGPU_E_ARG;
     fuifgpu_encode_options o;
     Lossy l;
     PaletteOpts pal;
+    AnimOpts anim;
     if (!read_encode_options(opt, o, 0) || !read_lossy_options(lossy, l) || !read_palette_options(palette, nch, pal)) return FUIFGPU_E_ARG;
+    if (const int rc = read_animation_options(anim_options, w, h, anim)) return rc;
     if (o.max_properties < 0 || o.max_properties > 2 * kMaxRefs) return FUIFGPU_E_ARG;
     if (o.max_tree_nodes < 1) o.max_tree_nodes = 4095;
     if (o.max_tree_nodes > kMaxNodes) o.max_tree_nodes = kMaxNodes;
@@ -985,9 +1092,13 @@ int fuifgpu_encode_image_ex(const int32_t *planes, int w, int h, int nch, int bi
     g_plane_h2d = g_plane_d2h = 0;
     Image img;
     bool squeezed = false;
-    const int rc = build_transformed_image(planes, w, h, nch, bit_depth, o, l, pal, img, squeezed);
+    const int rc = build_transformed_image(planes, w, h, nch, bit_depth, o, l, pal, anim, img, squeezed);
     if (rc != FUIFGPU_OK) return rc;
     return write_stream(img, nch, bit_depth, squeezed, o, blob_out, size_out);
+}
+int fuifgpu_encode_image_ex(const int32_t *planes, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
+                            const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette, uint8_t **blob_out, size_t *size_out) {
+    return fuifgpu_encode_animation(planes, w, h, nch, bit_depth, opt, lossy, palette, nullptr, blob_out, size_out);
 }
 int fuifgpu_encode_image_lossy(const int32_t *planes, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
                                const fuifgpu_lossy_options *lossy, uint8_t **blob_out, size_t *size_out) {
@@ -1102,11 +1213,17 @@ int learn_samples_device(Image &img, bool squeezed, const GroupCoder &gc, LearnS
 }
 // encoding/encoding.cpp:455-470: the fixed header fields into `head`, the transform list into `io`
 void begin_stream(const Image &img, int nch, int bit_depth, const fuifgpu_encode_options &o, Bytes &head, Bytes &io) {
-    for (const char *m = "FUIF"; *m; m++) head.put(*m);
+    for (const char *m = img.nb_frames > 1 ? "FUAF" : "FUIF"; *m; m++) head.put(*m);
     head.varint((size_t)(nch + '0'));
     head.varint((size_t)(bit_depth + '&'));
     head.varint((size_t)(img.w - 1));
     head.varint((size_t)(img.h - 1));
+    if (img.nb_frames > 1) {   // encoding.cpp:467-473: no per-frame numerators, no loop count
+        head.varint((size_t)(img.nb_frames - 2));
+        head.varint((size_t)(img.den - 1));
+        head.varint(0);
+        head.varint(0);
+    }
     head.varint(0);  // colormodel
     head.varint((size_t)o.max_properties);
     io.varint(img.transforms.size());
@@ -1287,12 +1404,14 @@ int write_streams_batch(std::vector<Image> &imgs, int nch, int bit_depth, const 
 // the batch entry points: planes[m] on the host, or (device_input) in device memory
 static int encode_images_common(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
                                 const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette, uint8_t **blobs_out, size_t *sizes_out,
-                                bool device_input) {
+                                bool device_input, const fuifgpu_animation_options *anim_options = nullptr) {
     if (!planes || !blobs_out || !sizes_out || n_images < 1 || w < 1 || h < 1 || nch < 1 || nch > 8 || bit_depth < 1 || bit_depth > 14) return FUIFGPU_E_ARG;
     fuifgpu_encode_options o;
     Lossy l;
     PaletteOpts pal;
     if (!read_encode_options(opt, o, 1) || !read_lossy_options(lossy, l) || !read_palette_options(palette, nch, pal)) return FUIFGPU_E_ARG;
+    AnimOpts anim;
+    if (const int arc = read_animation_options(anim_options, w, h, anim)) return arc;
     if (o.max_properties < 0 || o.max_properties > 2 * kMaxRefs) return FUIFGPU_E_ARG;
     if (o.max_tree_nodes < 1) o.max_tree_nodes = 4095;
     if (o.max_tree_nodes > kMaxNodes) o.max_tree_nodes = kMaxNodes;
@@ -1304,7 +1423,7 @@ static int encode_images_common(const int32_t *const *planes, int n_images, int 
     int rc = FUIFGPU_OK;
     for (int m = 0; m < n_images && rc == FUIFGPU_OK; m++) {
         bool sq = false;
-        rc = build_transformed_image(planes[m], w, h, nch, bit_depth, o, l, pal, imgs[(size_t)m], sq, device_input);
+        rc = build_transformed_image(planes[m], w, h, nch, bit_depth, o, l, pal, anim, imgs[(size_t)m], sq, device_input);
         squeezed[(size_t)m] = sq ? 1 : 0;
     }
     if (rc != FUIFGPU_OK) {   // (the pictures before the failed one may hold device-only channels)
@@ -1323,6 +1442,11 @@ extern "C" int fuifgpu_encode_images_ex(const int32_t *const *planes, int planes
                                         const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette,
                                         uint8_t **blobs_out, size_t *sizes_out) {
     return encode_images_common(planes, n_images, w, h, nch, bit_depth, opt, lossy, palette, blobs_out, sizes_out, planes_on_device != 0);
+}
+extern "C" int fuifgpu_encode_animations(const int32_t *const *frames, int on_device, int n_clips, int w, int frame_h, int nch, int bit_depth,
+                                         const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette,
+                                         const fuifgpu_animation_options *anim, uint8_t **blobs_out, size_t *sizes_out) {
+    return encode_images_common(frames, n_clips, w, frame_h, nch, bit_depth, opt, lossy, palette, blobs_out, sizes_out, on_device != 0, anim);
 }
 extern "C" int fuifgpu_encode_images(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
                                      uint8_t **blobs_out, size_t *sizes_out) {

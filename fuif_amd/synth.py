@@ -56,9 +56,35 @@ def graphic(w, h, channels=3, bits=8, seed=1, colors=32, step=1):
     return out
 
 
+def filmstrip(w, h, frames=3, channels=3, bits=8, seed=1, background="photographic", colors=24, noise=0.25, speckles=0, edits=()):
+    """Seeded animation, (F,C,H,W): what the Matching transform against the previous frame (transform/2dmatch.h:303-381) is made for.
+    A static background (photographic() or graphic() of the same seed) in every frame; a flat sprite of about w/6 x h/2 that moves
+    right by two samples per frame (wrapping); fresh noise in every frame over the rightmost `noise` share of the columns; `speckles`
+    single samples per frame changed at seeded places (short runs); then `edits`, rows [frame, y0, y1, x0, x1, d]: that region of that
+    frame becomes (background + d) mod 2^bits -- d = 0 puts the background back, which is how a test places runs of an exact length."""
+    rng = np.random.default_rng(seed)
+    maxval = (1 << bits) - 1
+    back = photographic(w, h, channels, bits, seed) if background == "photographic" else graphic(w, h, channels, bits, seed, colors=colors)
+    out = np.repeat(back[None], frames, axis=0)
+    sw, sh = max(3, w // 6), max(2, h // 2)
+    sx, sy = int(rng.integers(0, max(1, w - sw))), int(rng.integers(0, max(1, h - sh + 1)))
+    colour = rng.integers(0, maxval + 1, size=channels)
+    nw = int(round(noise * w))
+    for f in range(frames):
+        x0 = (sx + 2 * f) % max(1, w - sw)
+        out[f, :, sy:sy + sh, x0:x0 + sw] = colour[:, None, None]
+        if nw:
+            out[f, :, :, w - nw:] = rng.integers(0, maxval + 1, size=(channels, h, nw))
+        for _ in range(speckles):
+            out[f, :, int(rng.integers(0, h)), int(rng.integers(0, w))] = rng.integers(0, maxval + 1, size=channels)
+    for f, y0, y1, x0, x1, d in edits:
+        out[f, :, y0:y1, x0:x1] = (back[:, y0:y1, x0:x1] + d) % (maxval + 1)
+    return out.astype(np.int32)
+
+
 def from_recipe(recipe):
     """A picture from a description that fits in a JSON manifest (tests/golden/palette/manifest_palette.json), for inputs that are not one
-    call of the generators above:
+    call of the generators above ("filmstrip": the (F,C,H,W) frames of filmstrip() with the recipe's keywords):
       {"kind": "graphic" | "photographic", "w":, "h":, "channels":, "bits":, "seed":, ...their keywords, "floor_to": k}
           floor_to: every sample rounded down to a multiple of k (a sparse histogram on a photograph)
       {"kind": "full", "shape": [c, h, w], "value": v}            one flat value
@@ -69,6 +95,8 @@ def from_recipe(recipe):
     if kind == "stack":
         return np.concatenate([from_recipe(p) for p in recipe["parts"]], axis=0)
     kw = {k: v for k, v in recipe.items() if k not in ("kind", "floor_to")}
+    if kind == "filmstrip":
+        return filmstrip(**kw)
     img = {"graphic": graphic, "photographic": photographic}[kind](**kw)
     k = recipe.get("floor_to", 1)
     return (img // k * k).astype(np.int32)

@@ -406,6 +406,39 @@ int fuifgpu_encode_images_ex(const int32_t *const *planes, int planes_on_device,
  * FUIFGPU_E_ARG. */
 int fuifgpu_fwd_palette(const int32_t *const *planes_device, int nb, int64_t n_samples, int max_colors, int32_t *index_device,
                         int32_t *palette_host, int *n_colors, void *stream);
+/* ---- animations: what `fuif frame-%02d.ppm out.fuif` writes (encoding.cpp:458-473, fuif.cpp:440-448, transform/2dmatch.h:303-381) ----
+ * nb_frames pictures of w x frame_h are coded as one strip of w x (nb_frames * frame_h) under the magic "FUAF"; behind h-1 the header
+ * carries nb_frames-2, framerate-1, 0 (no per-frame numerators) and 0 loops.  With match_previous the Matching transform runs behind
+ * YCoCg and the palettes and in front of Squeeze, over all channels that are left: a meta-channel m of the strip's size goes in FRONT of
+ * the channel list (also in front of a palette), m.q = 2*frame_h^2 + (frame_h & 1) (the offset code of "one frame up"), m = 1 on every
+ * horizontal run of at least clamp(w/50, 5, 40) samples that equal the sample frame_h rows up in every channel; three erode sweeps unmark
+ * the rim of every matched region, and what keeps its mark is stored as 0 in every channel.  m is coded like a palette (predictor
+ * "left"); the Squeeze test of fuif.cpp:453 looks at m; Quantize leaves it alone.  The transform is written without parameters.
+ * With tree_mode 0 the bytes are those of `fuif -I 0 [-F framerate] [-M 0] ...` on the frames.  With opt->gpu_forward, and always for
+ * frames on the device, fuifgpu_fwd_match_frames' kernels do it on the writer's own copies; m stays on the device like any channel.
+ * Only the CLI's default (-M -1) and off (-M 0) are offered.  Deeper distances (-M -2, ...) are refused: the reference's back-fill
+ * (2dmatch.h:327-329) counts positions, not unmatched samples, so from the second distance on it overwrites samples an earlier distance
+ * matched with an offset nobody compared -- a lossless mode that loses pixels. */
+typedef struct {
+    uint32_t struct_size;    /* = sizeof(fuifgpu_animation_options) of the CALLER's header, versioned like fuifgpu_encode_options; these
+                                four fields are its first version: a smaller size, or one that is no multiple of 4, is FUIFGPU_E_ARG */
+    int32_t nb_frames;       /* >= 1; 1 writes exactly what fuifgpu_encode_image_ex writes (magic "FUIF", no Matching) */
+    int32_t framerate;       /* -F: frames per second, 0 = the CLI's 10; negative is FUIFGPU_E_ARG */
+    int32_t match_previous;  /* 1 = -M -1 (what the CLI does for several frames), 0 = -M 0; anything else is FUIFGPU_E_ARG (see above) */
+} fuifgpu_animation_options;
+/* frames: nb_frames x nch planes of w * frame_h int32, frame after frame (a contiguous (F, C, H, W) array).  anim == NULL: one frame.
+ * A strip of more than 2^31-1 samples per channel, or frame_h above 32767 (the offset code is an int), is FUIFGPU_E_ARG.
+ * fuifgpu_encode_animations: n clips of one shape in host memory or (on_device != 0) in device memory, through the batch writer like
+ * fuifgpu_encode_images_ex; the caller's frames are never written.  Found by symbol lookup: the ABI version does not change. */
+int fuifgpu_encode_animation(const int32_t *frames, int w, int frame_h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
+                             const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette, const fuifgpu_animation_options *anim,
+                             uint8_t **blob_out, size_t *size_out);
+int fuifgpu_encode_animations(const int32_t *const *frames, int on_device, int n_clips, int w, int frame_h, int nch, int bit_depth,
+                              const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette,
+                              const fuifgpu_animation_options *anim, uint8_t **blobs_out, size_t *sizes_out);
+/* the transform alone on raw device planes: n_planes (1..8) planes of a w x h strip of nb_frames (>= 2, dividing h) frames; match_dev
+ * (w * h int32) gets the match channel, and the planes are modified IN PLACE (matched samples become 0).  Asynchronous on stream */
+int fuifgpu_fwd_match_frames(const int32_t *const *planes_dev, int n_planes, int w, int h, int nb_frames, int32_t *match_dev, void *stream);
 /* host: the constant fuif.cpp:459-503 gives one channel -- squeeze_option = opt->squeeze (the OPTION, not whether the picture was large
  * enough to be squeezed), chroma_table = 1 for the chroma table, shift = hcshift + vcshift (capped at 15).  1 when both qualities are
  * >= 100.  A negative shift or a quality the entry points above refuse gives -FUIFGPU_E_ARG. */
