@@ -124,6 +124,26 @@ def make_animation_options(nb_frames, framerate=None, match_previous=True):
     return AnimationOptions(C.sizeof(AnimationOptions), int(nb_frames), int(framerate), int(match_previous))
 
 
+class YuvOptions(C.Structure):
+    """fuifgpu_yuv_options (include/fuifgpu.h): how the raw 4:2:0 frames of `fuif -y WxH[:b]` lie in memory, how many, and `-F framerate`"""
+    _fields_ = [("struct_size", C.c_uint32), ("layout", C.c_int32), ("pitch_y", C.c_int32), ("pitch_c", C.c_int32), ("nb_frames", C.c_int32),
+                ("framerate", C.c_int32)]
+
+
+YUV_LAYOUTS = {"i420": 0, "nv12": 1}
+
+
+def make_yuv_options(layout="i420", pitch_y=0, pitch_c=0, nb_frames=1, framerate=None):
+    """YuvOptions for the keywords of encode_yuv420 and its siblings.  layout: "i420" / "nv12", or the header's number (which the
+    library checks)"""
+    if framerate is None:
+        framerate = 0
+    elif not np.isfinite(framerate) or framerate < 0 or framerate != int(framerate):
+        raise FuifGpuError(4, "encode_yuv420_clip: the frame rate is a whole number of frames per second, 1 or more (None = the CLI's 10)")
+    code = YUV_LAYOUTS.get(layout.lower(), -1) if isinstance(layout, str) else int(layout)
+    return YuvOptions(C.sizeof(YuvOptions), code, int(pitch_y), int(pitch_c), int(nb_frames), int(framerate))
+
+
 def make_lossy_options(quality=None, chroma_quality=None):
     """LossyOptions for the two keywords of encode_image / encode_images: a missing quality is 100 (lossless luma), a missing
     chroma quality "same as quality" (the CLI's default, 101)"""
@@ -151,6 +171,7 @@ ABI_SYMBOLS = [
     "fuifgpu_encode_images_device", "fuifgpu_channel_stats", "fuifgpu_encode_plane_traffic",
     "fuifgpu_encode_image_ex", "fuifgpu_encode_images_ex", "fuifgpu_fwd_palette",
     "fuifgpu_encode_animation", "fuifgpu_encode_animations", "fuifgpu_fwd_match_frames",
+    "fuifgpu_encode_yuv420", "fuifgpu_unpack_yuv420", "fuifgpu_quantization_constant_yuv",
     "fuifgpu_plane_checksums", "fuifgpu_device_count", "fuifgpu_set_device", "fuifgpu_get_device", "fuifgpu_batch_device", "fuifgpu_peer_copy", "fuifgpu_batch_set_in_flight",
 ]
 
@@ -259,6 +280,9 @@ def lib():
     L.fuifgpu_encode_animation.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(PaletteOptions), C.POINTER(AnimationOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.fuifgpu_encode_animations.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(PaletteOptions), C.POINTER(AnimationOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.fuifgpu_fwd_match_frames.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.fuifgpu_encode_yuv420.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(YuvOptions), C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.fuifgpu_unpack_yuv420.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(YuvOptions), vp, vp, vp, vp, vp]
+    L.fuifgpu_quantization_constant_yuv.argtypes = [C.c_float, C.c_float, C.c_int, C.c_int, C.c_int]
     L.fuifgpu_encode_plane_traffic.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.fuifgpu_quantization_constant.argtypes = [C.c_float, C.c_float, C.c_int, C.c_int, C.c_int]
     L.fuifgpu_encode_image.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
@@ -711,6 +735,115 @@ def fwd_match_frames(plane_device_ptrs, w, h, nb_frames, match_device_ptr, strea
     nb = len(plane_device_ptrs)
     ptrs = (C.c_void_p * max(nb, 1))(*[int(p) if p else 0 for p in plane_device_ptrs])
     _check(lib().fuifgpu_fwd_match_frames(ptrs, nb, int(w), int(h), int(nb_frames), match_device_ptr, stream))
+
+
+def yuv420_bytes(w, h, bit_depth=8, layout="i420", pitch_y=0, pitch_c=0, nb_frames=1):
+    """bytes from the first sample of a raw 4:2:0 clip to its last one (the last row of the last plane carries no padding)"""
+    bps = 2 if bit_depth > 8 else 1
+    nv12 = make_yuv_options(layout).layout == 1
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    row_c = cw * bps * (2 if nv12 else 1)
+    py, pc = pitch_y or w * bps, pitch_c or row_c
+    frame = py * h + pc * ch * (1 if nv12 else 2)
+    last_plane = py * h + (0 if nv12 else pc * ch)
+    return (nb_frames - 1) * frame + last_plane + (ch - 1) * pc + row_c
+
+
+def _yuv_raw(frame, need):
+    """bytes, or a uint8 / 16-bit unsigned array (stored little-endian) -> contiguous uint8 array of at least `need` bytes"""
+    if isinstance(frame, (bytes, bytearray, memoryview)):
+        a = np.frombuffer(frame, dtype=np.uint8)
+    else:
+        a = np.asarray(frame)
+        if a.dtype.kind != "u" or a.dtype.itemsize > 2:
+            raise FuifGpuError(4, "encode_yuv420: a frame is bytes, or a uint8 / uint16 array")
+        a = np.ascontiguousarray(a.astype("<u2", copy=False) if a.dtype.itemsize == 2 else a).reshape(-1).view(np.uint8)
+    if a.size < need:
+        raise FuifGpuError(4, "encode_yuv420: the frame holds %d bytes, its geometry needs %d" % (a.size, need))
+    return a
+
+
+def _yuv_keywords(gpu_forward, gpu_entropy, squeeze=True, max_properties=12, tree_mode=1, max_tree_nodes=4095, index=False, split_bits=None,
+                  quality=None, chroma_quality=None):
+    """encode_image's keywords minus the colour and palette ones -> (EncodeOptions, LossyOptions or None)"""
+    split_bits = DEFAULT_SPLIT_BITS if split_bits is None else split_bits
+    opt = make_encode_options(0, int(squeeze), max_properties, tree_mode, max_tree_nodes, int(index), int(split_bits), int(gpu_forward), int(gpu_entropy))
+    return opt, (None if quality is None and chroma_quality is None else make_lossy_options(quality, chroma_quality))
+
+
+def _encode_yuv420_call(ptrs, on_device, w, h, bit_depth, yuv, opt, lossy):
+    n = len(ptrs)
+    arr = (C.c_void_p * max(n, 1))(*ptrs)
+    outs, sizes = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+    _check(lib().fuifgpu_encode_yuv420(arr, int(on_device), n, int(w), int(h), int(bit_depth), C.byref(yuv), C.byref(opt), _byref_or_none(lossy), outs, sizes))
+    return _take_blobs(outs, sizes, n)
+
+
+def encode_yuv420_batch(frames, w, h, bit_depth=8, layout="i420", pitch_y=0, pitch_c=0, nb_frames=1, framerate=None, gpu_forward=False,
+                        gpu_entropy=False, **keywords):
+    """raw YUV 4:2:0 pictures (or clips of nb_frames frames back to back) of one shape -> list of .fuif byte strings, the bytes
+    `fuif -y WxH[:b]` writes for each (fuifgpu_encode_yuv420).  A picture is bytes, or a uint8 / uint16 array: the Y plane, then Cb and Cr of
+    ((w+1)/2) x ((h+1)/2) samples (layout "i420") or one plane of Cb, Cr pairs ("nv12"); one byte per sample at 8 bits, two little-endian
+    above; pitch_y / pitch_c: bytes from row to row (0 = tight).  The other keywords are encode_image's minus the colour and palette ones.
+    gpu_forward: the raw frames are uploaded and unpacked on the GPU (one launch), forward Squeeze and Quantize run there;
+    with gpu_entropy a batch's pixel loops run in one launch pair.  Same bytes on every route."""
+    need = yuv420_bytes(w, h, bit_depth, layout, pitch_y, pitch_c, nb_frames)
+    raws = [_yuv_raw(f, need) for f in frames]
+    opt, lossy = _yuv_keywords(gpu_forward, gpu_entropy, **keywords)
+    yuv = make_yuv_options(layout, pitch_y, pitch_c, nb_frames, framerate)
+    return _encode_yuv420_call([a.ctypes.data for a in raws], 0, w, h, bit_depth, yuv, opt, lossy)
+
+
+def encode_yuv420(frame, w, h, bit_depth=8, layout="i420", pitch_y=0, pitch_c=0, **keywords):
+    """one raw YUV 4:2:0 frame -> .fuif bytes: encode_yuv420_batch of one picture"""
+    return encode_yuv420_batch([frame], w, h, bit_depth, layout, pitch_y, pitch_c, **keywords)[0]
+
+
+def encode_yuv420_clip(clip, w, h, nb_frames, framerate=None, bit_depth=8, layout="i420", pitch_y=0, pitch_c=0, **keywords):
+    """nb_frames raw frames back to back -> the bytes `fuif -M 0 [-F framerate] -y WxH[:b] v-%02d.yuv` writes: the frames stacked per channel
+    under the magic FUAF, no Matching transform (the reference's previous-frame matcher reads outside the chroma planes).  h must be even."""
+    return encode_yuv420_batch([clip], w, h, bit_depth, layout, pitch_y, pitch_c, nb_frames=nb_frames, framerate=framerate, **keywords)[0]
+
+
+def encode_yuv420_device(frames, w=None, h=None, bit_depth=8, layout="i420", pitch_y=0, pitch_c=0, nb_frames=1, framerate=None, **keywords):
+    """raw frames that already live in DEVICE memory (a hardware decoder's surfaces) -> list of .fuif byte strings, the bytes
+    encode_yuv420_batch writes for the same samples.  The frames are read, never written; the unpacked channels stay on the device until
+    the last coded byte (encode_plane_traffic: nothing goes up).  frames: a list of integer device pointers, or an object with data_ptr(),
+    a uint8 or 16-bit dtype, contiguous layout and shape (N, bytes or samples per picture) -- e.g. a torch uint8 / int16 tensor on the GPU."""
+    if hasattr(frames, "data_ptr"):
+        shape = tuple(int(v) for v in frames.shape)
+        item = 2 if "int16" in str(frames.dtype) else 1 if "uint8" in str(frames.dtype) else 0
+        if len(shape) != 2 or not item or (hasattr(frames, "is_contiguous") and not frames.is_contiguous()):
+            raise FuifGpuError(4, "encode_yuv420_device: a tensor must be contiguous uint8 / int16 of shape (N, elements per picture)")
+        if shape[1] * item < yuv420_bytes(w, h, bit_depth, layout, pitch_y, pitch_c, nb_frames):
+            raise FuifGpuError(4, "encode_yuv420_device: the tensor's rows are shorter than a picture")
+        ptrs = [frames.data_ptr() + k * shape[1] * item for k in range(shape[0])]
+    else:
+        ptrs = [int(p) if p else 0 for p in frames]
+    if w is None or h is None:
+        raise FuifGpuError(4, "encode_yuv420_device: w and h are needed")
+    opt, lossy = _yuv_keywords(1, 1, **keywords)
+    yuv = make_yuv_options(layout, pitch_y, pitch_c, nb_frames, framerate)
+    return _encode_yuv420_call(ptrs, 1, w, h, bit_depth, yuv, opt, lossy)
+
+
+def unpack_yuv420(frame_device_ptr, w, h, y_device_ptr, cb_device_ptr, cr_device_ptr, bit_depth=8, layout="i420", pitch_y=0, pitch_c=0,
+                  flag_device_ptr=None, stream=None):
+    """fuifgpu_unpack_yuv420: one raw 4:2:0 frame in DEVICE memory -> three tight int32 planes in device memory (w*h, and twice
+    ((w+1)/2) * ((h+1)/2) samples); flag_device_ptr: an int32 that becomes non-zero if a sample exceeds 2^bit_depth - 1; asynchronous on `stream`"""
+    yuv = make_yuv_options(layout, pitch_y, pitch_c)
+    _check(lib().fuifgpu_unpack_yuv420(frame_device_ptr, int(w), int(h), int(bit_depth), C.byref(yuv), y_device_ptr, cb_device_ptr, cr_device_ptr,
+                                      flag_device_ptr, stream))
+
+
+def quantization_constant_yuv(quality, chroma_quality=None, squeeze=True, chroma_table=False, shift=0):
+    """quantization_constant for `fuif -y` input (fuifgpu_quantization_constant_yuv: fuif.cpp:432-434 triples the luma factor and
+    divides the quality factor by three)"""
+    q = lib().fuifgpu_quantization_constant_yuv(float(quality), 101.0 if chroma_quality is None else float(chroma_quality), int(bool(squeeze)),
+                                                int(bool(chroma_table)), int(shift))
+    if q < 1:
+        _check(-q)
+    return q
 
 
 def channel_stats(plane_device_ptr, n_samples, stats_device_ptr, stream=None):

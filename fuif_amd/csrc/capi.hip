@@ -282,6 +282,27 @@ int fwd_palette_gpu(const int32_t *const *planes_device, int nb, int64_t n, int 
     *n_colors = (int)count;
     return FUIFGPU_OK;
 }
+// The writer's unpacking of every raw YUV frame of a call (writer.cpp): the flag word and behind it the job table in ONE device buffer,
+// like channel_stats_gpu -- one upload, one launch over (row segment, plane, frame), one word back.
+int unpack_yuv420_gpu(const YuvJob *jobs_host, int n_jobs, const YuvGeom &g, int *flag_host) {
+    *flag_host = 0;
+    if (n_jobs <= 0) return FUIFGPU_OK;
+    std::vector<uint8_t> host(16 + sizeof(YuvJob) * (size_t)n_jobs, 0);   // (the table behind the flag starts 16-byte aligned)
+    memcpy(host.data() + 16, jobs_host, sizeof(YuvJob) * (size_t)n_jobs);
+    uint8_t *dev = nullptr;
+    HIPCHK(hipMalloc((void **)&dev, host.size()));
+    hipError_t e = hipMemcpy(dev, host.data(), host.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_unpack_yuv420(reinterpret_cast<const YuvJob *>(dev + 16), n_jobs, YuvJob{}, g, reinterpret_cast<int32_t *>(dev), nullptr);
+        e = hipGetLastError();
+    }
+    int32_t flag = 0;
+    if (e == hipSuccess) e = hipMemcpy(&flag, dev, sizeof(flag), hipMemcpyDeviceToHost);   // waits for the kernel
+    hipFree(dev);
+    if (e != hipSuccess) return hip_fail(e, "unpack_yuv420_gpu");
+    *flag_host = flag != 0;
+    return FUIFGPU_OK;
+}
 int dev_copy(void *dst_device, const void *src_device, size_t bytes) {
     if (bytes) HIPCHK(hipMemcpy(dst_device, src_device, bytes, hipMemcpyDeviceToDevice));
     return FUIFGPU_OK;
@@ -1228,6 +1249,17 @@ int fuifgpu_fwd_match_frames(const int32_t *const *planes_dev, int n_planes, int
     mp.nb = n_planes;
     for (int c = 0; c < n_planes; c++) { if (!planes_dev[c]) return FUIFGPU_E_ARG; mp.p[c] = const_cast<int32_t *>(planes_dev[c]); }
     launch_fwd_match_frames(mp, w, h, h / nb_frames, 1, 0, match_dev, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return FUIFGPU_OK;
+}
+int fuifgpu_unpack_yuv420(const void *frame_device, int w, int h, int bit_depth, const fuifgpu_yuv_options *yuv, int32_t *y_out, int32_t *cb_out,
+                          int32_t *cr_out, int32_t *flag_device, void *stream) {
+    if (w < 0 || h < 0) return FUIFGPU_E_ARG;
+    if ((int64_t)w * h == 0) return FUIFGPU_OK;
+    YuvGeom g;
+    OKCHK(yuv_geometry(yuv, w, h, bit_depth, true, g, nullptr));
+    if (!frame_device || !y_out || !cb_out || !cr_out) return FUIFGPU_E_ARG;
+    launch_unpack_yuv420(nullptr, 1, YuvJob{static_cast<const uint8_t *>(frame_device), {y_out, cb_out, cr_out}}, g, flag_device, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return FUIFGPU_OK;
 }

@@ -184,6 +184,26 @@ struct StatsRec {
 // every record in one launch and the triples back with one copy (capi.hip): stats_host gets n_recs triples, each preset to what
 // Chan::minmax gives an empty channel ({INT32_MAX, INT32_MIN + 1, 0})
 int channel_stats_gpu(const StatsRec *recs, int n_recs, int32_t *stats_host);
+// The writer's unpacking of raw YUV 4:2:0 frames on the GPU (transforms.hip k_unpack_yuv420; import/read_yuv.h:29-63).  One job = one
+// picture: `src` (device) holds YuvGeom::nb_frames frames back to back, frame f's samples go to out[0..2] + f * (the plane's samples)
+struct YuvJob {
+    const uint8_t *src;
+    int32_t *out[3];
+};
+struct YuvGeom {
+    int32_t w, h, cw, ch;          // luma and chroma plane sizes, cw = (w+1)/2, ch = (h+1)/2
+    int32_t bytes, nv12, maxval;   // bytes per sample (1 or 2, little-endian); nv12: the chroma samples are one plane of Cb, Cr pairs
+    int32_t nb_frames;
+    int64_t pitch_y, pitch_c;      // row pitches in bytes (NV12: pitch_c of the interleaved plane)
+    int64_t frame_bytes;           // from one frame to the next
+    int64_t row_bytes(bool chroma) const { return chroma ? (int64_t)cw * bytes * (nv12 ? 2 : 1) : (int64_t)w * bytes; }
+};
+// every frame of every job in one launch (capi.hip): jobs_host[k].src / out are device pointers; *flag_host = 1 if a sample exceeded
+// g.maxval.  Synchronous (null stream)
+int unpack_yuv420_gpu(const YuvJob *jobs_host, int n_jobs, const YuvGeom &g, int *flag_host);
+// fuifgpu_yuv_options (NULL = tight I420, one frame) + the frame's size and depth -> the geometry, checked (writer.cpp): FUIFGPU_E_ARG with a
+// message for a bad struct_size, layout, pitch, depth, frame count or a clip of odd height.  one_frame: nb_frames is not looked at.  *framerate (may be NULL): the option's (0 = the CLI's)
+int yuv_geometry(const void *yuv_options, int w, int h, int bit_depth, bool one_frame, YuvGeom &g, int *framerate);
 // The writer's forward Palette on device planes (capi.hip; transforms.hip k_palette_collect / k_palette_index): the distinct tuples of
 // planes[0..nb-1] (nb 1..4, n samples each).  More than max_colors: *n_colors = -1 and nothing is written.  Otherwise rows = the palette
 // (rows[c * *n_colors + k], the reference's order) and index_device[i] = the colour of sample i (may alias planes[0]).  Synchronous

@@ -1092,6 +1092,104 @@ void launch_channel_stats(const StatsRec *dev_table, int n_recs, StatsRec one, i
     if (total_blocks <= 0) return;
     hipLaunchKernelGGL(k_channel_stats, dim3((unsigned)total_blocks), dim3(256), 0, stream, dev_table, n_recs, one, dev_stats);
 }
+// import/read_yuv.h:29-63 on the GPU: raw 4:2:0 frames (8-bit samples, or 16-bit little-endian ones; planar, or with the chroma samples
+// as one plane of Cb, Cr pairs; rows `pitch` bytes apart) -> tight int32 planes.  Bandwidth bound, 1.5-3 bytes in and 6 out per pixel; no LDS.
+// The grid runs over (row segment, plane, frame): a wavefront takes one row segment, a lane one aligned load of 4 samples (4 or 8 bytes)
+// or, in a plane of pairs, of 4 pairs (8 or 16 bytes) -- consecutive lanes read consecutive words, a wavefront 256 B to 1 KiB per
+// instruction -- and stores them as int32x4, one store per output plane, wherever the destination is on a 16-byte boundary (it is
+// for tight frames whose width is a multiple of 4, a hardware decoder's; else four dword stores, still consecutive across the lanes).
+// A row starts at base + y * pitch, on any byte (a row of 16-bit samples on an odd byte goes one by one as a whole): the ELEMENTS (samples of a row, Cb and Cr alike) in
+// front of the first aligned word and behind the last whole one, at most 3 (7 in a plane of pairs) each, go one by one, byte loads, in
+// the first lanes of the row's first segment, as fwd_quantize_plane treats the ends of a plane.  No load touches a byte outside
+// [row, row + row bytes): the caller's surface may end with its last row.  In a plane of pairs whose first aligned word starts with a
+// Cr sample the odd elements of every word are the Cb samples and the Cr samples belong to the pair before.
+template <int BYTES>
+__device__ __forceinline__ uint32_t yuv_element(const uint32_t *words, int i) {   // element i of a loaded vector (little-endian)
+    return BYTES == 1 ? (words[i >> 2] >> (8 * (i & 3))) & 0xFFu : (words[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
+}
+template <int BYTES>
+__device__ __forceinline__ uint32_t yuv_element_at(const uint8_t *p) {   // one by one: byte loads, any address
+    return BYTES == 1 ? p[0] : (uint32_t)p[0] | ((uint32_t)p[1] << 8);
+}
+// (a compiler vector, one 16-byte store instruction in the IR: written as an int4 struct the aligned form is four member stores, which the
+// optimiser merges with the four dword stores of the other branch -- and no dwordx4 store is left, profiles/yuv_forward.txt)
+typedef int32_t yuv_quad_t __attribute__((vector_size(16)));
+__device__ __forceinline__ void store_quad(int32_t *dst, int a, int b, int c, int d) {
+    if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) { const yuv_quad_t v = {a, b, c, d}; *reinterpret_cast<yuv_quad_t *>(dst) = v; }
+    else { dst[0] = a; dst[1] = b; dst[2] = c; dst[3] = d; }
+}
+// one row segment: `n` elements at `row`; PAIRS: element e is component e & 1 of pair e >> 1, which goes to out0 / out1 [e >> 1]; else to out0[e].
+// k: the lane's vector among the row's; first_segment: this wavefront also takes the row's ends.  Returns whether a sample exceeded maxval
+template <int BYTES, bool PAIRS>
+__device__ __forceinline__ bool unpack_row_segment(const uint8_t *row, int64_t n, int32_t *out0, int32_t *out1, int64_t k, bool first_segment, int lane,
+                                                   uint32_t maxval) {
+    constexpr int E = PAIRS ? 8 : 4, VB = E * BYTES;            // elements and bytes of one vector load
+    const int64_t to_aligned = (int64_t)((VB - (reinterpret_cast<uintptr_t>(row) & (VB - 1))) & (VB - 1)) / BYTES;
+    const bool split_samples = BYTES == 2 && (reinterpret_cast<uintptr_t>(row) & 1);   // 16-bit samples on odd addresses: no aligned word holds whole ones, the row is all head
+    const int64_t head = to_aligned < n && !split_samples ? to_aligned : n, nvec = (n - head) / E, tail = n - head - nvec * E;
+    uint32_t over = 0;
+    if (k < nvec) {
+        const int64_t e0 = head + k * E;
+        uint32_t words[VB / 4];
+        if constexpr (VB == 4) words[0] = *reinterpret_cast<const uint32_t *>(row + e0 * BYTES);
+        else if constexpr (VB == 8) { const uint2 v = *reinterpret_cast<const uint2 *>(row + e0 * BYTES); words[0] = v.x; words[1] = v.y; }
+        else {
+            const int4 v = *reinterpret_cast<const int4 *>(row + e0 * BYTES);
+            words[0] = (uint32_t)v.x; words[1] = (uint32_t)v.y; words[2] = (uint32_t)v.z; words[3] = (uint32_t)v.w;
+        }
+        uint32_t s[E];
+        for (int i = 0; i < E; i++) { s[i] = yuv_element<BYTES>(words, i); over |= s[i] > maxval; }
+        if constexpr (!PAIRS) store_quad(out0 + e0, (int)s[0], (int)s[1], (int)s[2], (int)s[3]);
+        else {
+            // even e0: elements 0, 2, 4, 6 are Cb of pairs e0/2 .. e0/2 + 3 and the odd ones their Cr; odd e0: the odd elements are Cb of pairs
+            // (e0+1)/2 .., the even ones Cr of the pairs one before
+            const bool swapped = (e0 & 1) != 0;
+            store_quad((swapped ? out1 : out0) + (e0 >> 1), (int)s[0], (int)s[2], (int)s[4], (int)s[6]);
+            store_quad((swapped ? out0 : out1) + ((e0 + 1) >> 1), (int)s[1], (int)s[3], (int)s[5], (int)s[7]);
+        }
+    }
+    if (first_segment)   // the ends: at most E - 1 elements each (a row of split samples: all of it), one per lane and pass
+        for (int64_t i = lane; i < head + tail; i += 64) {
+            const int64_t e = i < head ? i : i + nvec * E;
+            const uint32_t v = yuv_element_at<BYTES>(row + e * BYTES);
+            over |= v > maxval;
+            if (!PAIRS) out0[e] = (int32_t)v;
+            else ((e & 1) ? out1 : out0)[e >> 1] = (int32_t)v;
+        }
+    return over != 0;
+}
+__global__ __launch_bounds__(256) void k_unpack_yuv420(const YuvJob *table, YuvJob one, YuvGeom g, int segs, int32_t *flag) {
+    const int job = blockIdx.z / g.nb_frames, f = blockIdx.z - job * g.nb_frames;
+    if (table) one = table[job];
+    const int p = blockIdx.y;                       // 0: Y; planar: 1 Cb, 2 Cr; nv12: 1 the plane of pairs
+    const int pw = p ? g.cw : g.w, ph = p ? g.ch : g.h;
+    const int rows4 = blockIdx.x / segs, seg = blockIdx.x - rows4 * segs;
+    const int y = rows4 * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // a block: four rows, one wavefront each
+    if (y >= ph) return;
+    const bool pairs = p && g.nv12;
+    const int64_t plane_at = p == 0 ? 0 : g.pitch_y * g.h + (p == 2 ? g.pitch_c * g.ch : 0);
+    const uint8_t *row = one.src + f * g.frame_bytes + plane_at + y * (p ? g.pitch_c : g.pitch_y);
+    const int64_t plane_samples = (int64_t)pw * ph, at = f * plane_samples + (int64_t)y * pw;
+    int32_t *out0 = one.out[p] + at, *out1 = pairs ? one.out[2] + at : nullptr;
+    const int64_t k = (int64_t)seg * 64 + lane;
+    bool over;
+    if (g.bytes == 1) over = pairs ? unpack_row_segment<1, true>(row, 2 * (int64_t)pw, out0, out1, k, seg == 0, lane, (uint32_t)g.maxval)
+                                   : unpack_row_segment<1, false>(row, pw, out0, out1, k, seg == 0, lane, (uint32_t)g.maxval);
+    else over = pairs ? unpack_row_segment<2, true>(row, 2 * (int64_t)pw, out0, out1, k, seg == 0, lane, (uint32_t)g.maxval)
+                      : unpack_row_segment<2, false>(row, pw, out0, out1, k, seg == 0, lane, (uint32_t)g.maxval);
+    if (over && flag) atomicOr(flag, 1);   // (rare: a lane that met one)
+}
+void launch_unpack_yuv420(const YuvJob *dev_table, int n_jobs, YuvJob one, const YuvGeom &g, int32_t *dev_flag, hipStream_t stream) {
+    if (n_jobs <= 0 || g.w <= 0 || g.h <= 0 || g.nb_frames <= 0 || g.nb_frames > 65535) return;   // (the callers refuse longer clips)
+    // a luma row has at most w / 4 whole vectors, a chroma row or a row of pairs no more; every row has a first segment for its ends
+    const int segs = std::max(1, (g.w / 4 + 63) / 64);
+    const int64_t frames = (int64_t)n_jobs * g.nb_frames;
+    for (int64_t z0 = 0; z0 < frames; z0 += 65535 / g.nb_frames * g.nb_frames) {   // (grid.z holds 65535: whole jobs per launch)
+        const int64_t nz = std::min<int64_t>(frames - z0, 65535 / g.nb_frames * g.nb_frames);
+        hipLaunchKernelGGL(k_unpack_yuv420, dim3((unsigned)(segs * ((g.h + 3) / 4)), g.nv12 ? 2u : 3u, (unsigned)nz), dim3(256), 0, stream,
+                           dev_table ? dev_table + z0 / g.nb_frames : nullptr, one, g, segs, dev_flag);
+    }
+}
 // ---------------------------------------------------------------------------------------------
 // Forward Palette (transform/palette.h:92-142): which colour tuples occur, then every pixel's colour number.  The reference inserts every
 // pixel into a std::set and searches the palette linearly per pixel; here the set is built by all lanes at once and the order of the

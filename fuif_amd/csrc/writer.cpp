@@ -29,6 +29,9 @@
 // with maxdist = -1); on the GPU routes k_match_frames_runs / _erode / _apply do it.  Only that distance and "off" are offered: from the
 // second distance on the reference's back-fill (2dmatch.h:327-329) counts positions, not unmatched samples, and overwrites samples an
 // earlier distance matched with an offset that was never compared -- a lossless mode that loses pixels, which is not reproduced.
+// Raw YUV 4:2:0 frames (fuifgpu_encode_yuv420, `fuif -y WxH[:b]`; import/read_yuv.h:29-63, fuif.cpp:431-435): three channels of unequal geometry
+// under a recorded [YCbCr, ChromaSubsample] pair, no colour transform, no palettes, no Matching; on the GPU routes k_unpack_yuv420 unpacks the
+// raw bytes of every frame of a call in one launch (the section at the end of this file).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -183,6 +186,22 @@ struct Image {
     int nb_frames = 1, den = 10;   // an animation: h = nb_frames frames one above the other; den: frames per second (image.h `den`)
     std::vector<TransformDesc> transforms;
     int downscales[6];
+    bool stale_tail = false;   // write what the reference's buffer holds behind the last group (StaleTail below); the .yuv route sets it
+};
+
+// The reference codes every group compressed first and, when that does not pay, seeks back and writes it again uncompressed
+// (encoding.cpp:545-551) -- but its BlobIO never shrinks (fileio.h:236-263: bytes_used is a high-water mark), so where the shorter
+// second form of the LAST groups ends before the first one did, the file goes on with the abandoned form's bytes.  No decoder reads
+// them.  A .yuv stream ends with its smallest channels (the chroma residuals, or 3 x 2 chroma planes), where this is common, so that
+// route reproduces them: `shadow` is the reference's buffer as far as abandoned forms reached.
+struct StaleTail {
+    std::vector<uint8_t> shadow;
+    void abandoned(size_t at, const uint8_t *bytes, size_t n) {
+        if (shadow.size() < at + n) shadow.resize(at + n, 0);
+        memcpy(shadow.data() + at, bytes, n);
+    }
+    // what lies behind a stream of `end` bytes
+    std::vector<uint8_t> behind(size_t end) const { return end < shadow.size() ? std::vector<uint8_t>(shadow.begin() + end, shadow.end()) : std::vector<uint8_t>(); }
 };
 
 // ---- forward transforms ------------------------------------------------------------------------
@@ -479,8 +498,12 @@ int fwd_match_frames(Image &img, bool on_gpu) {
 struct Lossy {
     bool active = false;               // fuif.cpp:459: quality < 100 || cquality < 100
     float quality = 100.f, cquality = 100.f;
+    bool yuv = false;                  // .yuv input (image_type == 2): the two factors of fuif.cpp:432-434
 };
 const float squeeze_quality_factor = 0.3, squeeze_luma_factor = 1.2;   // fuif.cpp:70-71
+// fuif.cpp:432-434, "make chroma more important" for .yuv input: `squeeze_luma_factor *= 3.0; squeeze_quality_factor /= 3.0;` -- the float
+// variables above, each updated through a double expression and stored back to float
+const float yuv_squeeze_quality_factor = (float)((double)squeeze_quality_factor / 3.0), yuv_squeeze_luma_factor = (float)((double)squeeze_luma_factor * 3.0);
 const float squeeze_luma_qtable[16] = {163.84, 81.92, 40.96, 20.48, 10.24, 5.12, 2.56, 1.28, 0.64, 0.32, 0.16, 0.08, 0.04, 0.02, 0.01, 0.005};   // fuif.cpp:74
 const float squeeze_chroma_qtable[16] = {1024, 512, 256, 128, 64, 32, 16, 8, 4, 2, 1, 0.5, 0.5, 0.5, 0.5, 0.5};                                  // fuif.cpp:76
 
@@ -495,8 +518,9 @@ float quality_to_scale(float x, bool squeeze_option) {
 int quantization_constant(const Lossy &l, bool squeeze_option, bool chroma_table, int shift) {  // fuif.cpp:492-500
     if (shift > 15) shift = 15;
     int q;
-    if (chroma_table) q = (int)(quality_to_scale(l.cquality, squeeze_option) * squeeze_quality_factor * squeeze_chroma_qtable[shift]);
-    else q = (int)(quality_to_scale(l.quality, squeeze_option) * squeeze_quality_factor * squeeze_luma_factor * squeeze_luma_qtable[shift]);
+    const float quality_factor = l.yuv ? yuv_squeeze_quality_factor : squeeze_quality_factor, luma_factor = l.yuv ? yuv_squeeze_luma_factor : squeeze_luma_factor;
+    if (chroma_table) q = (int)(quality_to_scale(l.cquality, squeeze_option) * quality_factor * squeeze_chroma_qtable[shift]);
+    else q = (int)(quality_to_scale(l.quality, squeeze_option) * quality_factor * luma_factor * squeeze_luma_qtable[shift]);
     return q < 1 ? 1 : q;
 }
 // the caller's two numbers -> Lossy; false: NaN, negative, or a quality above 100 (only the chroma quality may be: "same as quality", fuif.cpp:247)
@@ -920,6 +944,9 @@ int write_stream(Image &img, int nch, int bit_depth, bool squeezed, const fuifgp
 }
 }  // namespace fuifgpu
 
+static int squeeze_quantize_and_fetch(fuifgpu::Image &img, const fuifgpu_encode_options &o, const fuifgpu::Lossy &lossy, bool colour_option, bool on_gpu,
+                                      bool keep_resident, bool &squeezed, int rc);
+
 // planes -> Image with the CLI's default forward transforms applied (fuif.cpp:380-455) and, with a quality, its Quantize (fuif.cpp:459-503),
 // on the host or on the GPU.  device_input: `planes` is device memory -- the forward transforms run on working copies there (gpu_forward is
 // implied) and the transformed channels STAY there, device-only (Chan::resident), for write_streams_batch
@@ -973,6 +1000,14 @@ static int build_transformed_image(const int32_t *planes, int w, int frame_h, in
     }
     if (rc == FUIFGPU_OK && pal.post > 0.f) rc = compact_channels(img, pal.post, false, on_gpu);   // fuif.cpp:418-430
     if (rc == FUIFGPU_OK && anim.nb_frames > 1 && anim.match) rc = fwd_match_frames(img, on_gpu);   // fuif.cpp:440-448
+    return squeeze_quantize_and_fetch(img, o, lossy, o.ycocg != 0, on_gpu, device_input, squeezed, rc);
+}
+// the end of every input route (fuif.cpp:450-503): default Squeeze, Quantize, and the transformed channels back from the GPU unless they
+// stay there (keep_resident).  The channels may differ in geometry from the start (.yuv input).  colour_option: `colorspace != 0`, components
+// 1 and 2 take the chroma table.  rc: what the steps before have come to -- after a failure only the device buffers are released
+static int squeeze_quantize_and_fetch(fuifgpu::Image &img, const fuifgpu_encode_options &o, const fuifgpu::Lossy &lossy, bool colour_option, bool on_gpu,
+                                      bool keep_resident, bool &squeezed, int rc) {
+    using namespace fuifgpu;
     squeezed = false;
     if (rc == FUIFGPU_OK && o.squeeze && (int64_t)img.ch[0].w * img.ch[0].h > 20) {  // fuif.cpp:453: channel[0] -- the match channel or a palette, once there is one
         std::vector<int> params = default_squeeze_params(img);
@@ -981,8 +1016,8 @@ static int build_transformed_image(const int32_t *planes, int w, int frame_h, in
         squeezed = true;
     }
     std::vector<char> all_zero(img.ch.size(), 0);   // gpu_forward + lossy: channels whose quotients are all 0 stay on the device
-    if (rc == FUIFGPU_OK && lossy.active) rc = fwd_quantize(img, lossy, o.squeeze != 0, o.ycocg != 0, on_gpu, all_zero);   // fuif.cpp:459-503
-    if (on_gpu && (!device_input || rc != FUIFGPU_OK)) {
+    if (rc == FUIFGPU_OK && lossy.active) rc = fwd_quantize(img, lossy, o.squeeze != 0, colour_option, on_gpu, all_zero);   // fuif.cpp:459-503
+    if (on_gpu && (!keep_resident || rc != FUIFGPU_OK)) {
         for (size_t k = 0; k < img.ch.size(); k++) {
             Chan &ch = img.ch[k];
             if (rc == FUIFGPU_OK && ch.dev) {
@@ -1237,7 +1272,8 @@ void note_responsive(const Image &img, int i, size_t after, int responsive[5]) {
     for (int s = 0; s < 5; s++) if (img.downscales[s] == i) responsive[s] = (int)after;
 }
 // encoding.cpp:552-573: the responsive offsets behind the header, the groups, the optional index trailer -> one malloc'ed blob
-int finish_stream(Bytes &head, const Bytes &io, int responsive[5], std::vector<GroupEntry> &group_at, bool emit_index, uint8_t **blob_out, size_t *size_out) {
+int finish_stream(Bytes &head, const Bytes &io, int responsive[5], std::vector<GroupEntry> &group_at, bool emit_index, uint8_t **blob_out, size_t *size_out,
+                  const std::vector<uint8_t> &stale = std::vector<uint8_t>()) {
     int rel = 0;
     for (int s = 0; s < 5; s++) {
         if (responsive[s] < 0) responsive[s] = (int)io.b.size();
@@ -1250,12 +1286,13 @@ int finish_stream(Bytes &head, const Bytes &io, int responsive[5], std::vector<G
         for (GroupEntry &g : group_at) g.start += (uint32_t)head.b.size();
         build_index_trailer(group_at, trailer);
     }
-    const size_t total = head.b.size() + io.b.size() + trailer.size();
+    const size_t total = head.b.size() + io.b.size() + stale.size() + trailer.size();
     uint8_t *blob = (uint8_t *)malloc(total ? total : 1);
     if (!blob) return FUIFGPU_E_NOMEM;
     memcpy(blob, head.b.data(), head.b.size());
     memcpy(blob + head.b.size(), io.b.data(), io.b.size());
-    if (!trailer.empty()) memcpy(blob + head.b.size() + io.b.size(), trailer.data(), trailer.size());
+    if (!stale.empty()) memcpy(blob + head.b.size() + io.b.size(), stale.data(), stale.size());   // (Image::stale_tail)
+    if (!trailer.empty()) memcpy(blob + head.b.size() + io.b.size() + stale.size(), trailer.data(), trailer.size());
     *blob_out = blob;
     *size_out = total;
     return FUIFGPU_OK;
@@ -1283,6 +1320,7 @@ int write_stream(Image &img, int nch, int bit_depth, bool squeezed, const fuifgp
     begin_stream(img, nch, bit_depth, o, head, io);
     int responsive[5] = {-1, -1, -1, -1, -1};
     std::vector<GroupEntry> group_at;  // group starts relative to `io` (made absolute below)
+    StaleTail stale;
     const int n = (int)img.ch.size();
     for (int i = 0; i < n; i++) {
         Chan &c = img.ch[i];
@@ -1296,13 +1334,14 @@ int write_stream(Image &img, int nch, int bit_depth, bool squeezed, const fuifgp
         if (c.maxval > c.minval) ubits = pixels * (ilog2u((uint32_t)(c.maxval - c.minval)) + 1) + 16;
         if (bits >= ubits) {
             // encoding.cpp:545-551: roll back, store uncompressed; a trivial channel: the reference re-encodes it "uncompressed" too (compress bit = 0)
+            if (img.stale_tail) stale.abandoned(before, io.b.data() + before, io.b.size() - before);
             io.b.resize(before);
             encode_group(io, img, i, predictor, false, gc, header_pos);
         }
         note_responsive(img, i, io.b.size(), responsive);
     }
     if (gpu_rc != FUIFGPU_OK) return gpu_rc;   // no host route behind the GPU pixel loop: the caller asked for it
-    return finish_stream(head, io, responsive, group_at, o.emit_index != 0, blob_out, size_out);
+    return finish_stream(head, io, responsive, group_at, o.emit_index != 0, blob_out, size_out, stale.behind(io.b.size()));
 }
 
 
@@ -1367,6 +1406,7 @@ int write_streams_batch(std::vector<Image> &imgs, int nch, int bit_depth, const 
         begin_stream(img, nch, bit_depth, o, head, io);
         int responsive[5] = {-1, -1, -1, -1, -1};
         std::vector<GroupEntry> group_at;
+        StaleTail stale;
         for (PendingGroup &pg : pending[m]) {
             const int i = pg.channel;
             Chan &c = img.ch[i];
@@ -1382,8 +1422,10 @@ int write_streams_batch(std::vector<Image> &imgs, int nch, int bit_depth, const 
                 rac.flush();
                 const float bits = (g.b.size() - pg.header_len) * 8.0f, pixels = (float)c.w * c.h;
                 const float ubits = pixels * (ilog2u((uint32_t)(c.maxval - c.minval)) + 1) + 16;
-                if (bits >= ubits) uncompressed = true;   // encoding.cpp:545-551: roll back, store uncompressed
-                else io.b.insert(io.b.end(), g.b.begin(), g.b.end());
+                if (bits >= ubits) {   // encoding.cpp:545-551: roll back, store uncompressed
+                    uncompressed = true;
+                    if (img.stale_tail) stale.abandoned(before, g.b.data(), g.b.size());
+                } else io.b.insert(io.b.end(), g.b.begin(), g.b.end());
             }
             if (uncompressed) {
                 size_t header_pos = 0;
@@ -1392,7 +1434,7 @@ int write_streams_batch(std::vector<Image> &imgs, int nch, int bit_depth, const 
             note_responsive(img, i, io.b.size(), responsive);
         }
         if (gpu_rc != FUIFGPU_OK) return gpu_rc;
-        rc = finish_stream(head, io, responsive, group_at, o.emit_index != 0, &blobs_out[m], &sizes_out[m]);
+        rc = finish_stream(head, io, responsive, group_at, o.emit_index != 0, &blobs_out[m], &sizes_out[m], stale.behind(io.b.size()));
         if (rc != FUIFGPU_OK) return rc;
     }
     return FUIFGPU_OK;
@@ -1455,4 +1497,162 @@ extern "C" int fuifgpu_encode_images(const int32_t *const *planes, int n_images,
 extern "C" int fuifgpu_encode_images_device(const int32_t *const *planes_device, int n_images, int w, int h, int nch, int bit_depth,
                                             const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out) {
     return encode_images_common(planes_device, n_images, w, h, nch, bit_depth, opt, lossy, nullptr, blobs_out, sizes_out, true);
+}
+
+// ---- YUV 4:2:0 video frames: what `fuif -y WxH[:b]` writes (import/read_yuv.h:29-63, fuif.cpp:277-283, 309-329, 431-435) ------------------
+// Three channels of unequal geometry from the start -- Y w x h, Cb and Cr (w+1)/2 x (h+1)/2 with hshift = vshift = 1 -- under a transform
+// list that begins [YCbCr, ChromaSubsample{0}] (recorded, not computed); no colour transform, no palettes, no Matching (2dmatch.h:321-322
+// indexes the chroma planes with luma coordinates); from Squeeze on, the end of every input route (squeeze_quantize_and_fetch).
+namespace fuifgpu {
+int yuv_geometry(const void *yuv_options, int w, int h, int bit_depth, bool one_frame, YuvGeom &g, int *framerate) {
+    fuifgpu_yuv_options y;
+    memset(&y, 0, sizeof(y));
+    if (yuv_options) {
+        const uint32_t sz = static_cast<const fuifgpu_yuv_options *>(yuv_options)->struct_size;
+        if (sz < sizeof(uint32_t) || (sz & 3u)) return fail_with_message(FUIFGPU_E_ARG, "yuv420: struct_size of fuifgpu_yuv_options");
+        memcpy(&y, yuv_options, sz < sizeof(y) ? sz : sizeof(y));
+        if (sz <= offsetof(fuifgpu_yuv_options, nb_frames)) y.nb_frames = 1;   // a struct that ends before the field
+    } else y.nb_frames = 1;
+    if (one_frame) y.nb_frames = 1;
+    if (w < 1 || h < 1 || bit_depth < 8 || bit_depth > 14) return fail_with_message(FUIFGPU_E_ARG, "yuv420: a frame of at least 1 x 1 samples of 8 to 14 bits");
+    if (y.layout != 0 && y.layout != 1) return fail_with_message(FUIFGPU_E_ARG, "yuv420: layout is 0 (I420) or 1 (NV12)");
+    if (y.nb_frames < 1 || y.nb_frames > 65535 || y.framerate < 0) return fail_with_message(FUIFGPU_E_ARG, "yuv420: 1 to 65535 frames, a frame rate of 0 or more");
+    if (y.nb_frames > 1 && (h & 1))
+        return fail_with_message(FUIFGPU_E_ARG, "yuv420: a clip needs an even frame height (the stacked chroma planes would not be (H+1)/2 rows of the strip)");
+    if ((int64_t)w * h * y.nb_frames > INT32_MAX || (int64_t)h * y.nb_frames > INT32_MAX) return fail_with_message(FUIFGPU_E_ARG, "yuv420: more than 2^31-1 samples in a channel");
+    g = YuvGeom{};
+    g.w = w; g.h = h; g.cw = (w + 1) / 2; g.ch = (h + 1) / 2;
+    g.bytes = bit_depth > 8 ? 2 : 1; g.nv12 = y.layout; g.maxval = (1 << bit_depth) - 1; g.nb_frames = y.nb_frames;
+    g.pitch_y = y.pitch_y ? y.pitch_y : g.row_bytes(false);
+    g.pitch_c = y.pitch_c ? y.pitch_c : g.row_bytes(true);
+    if (g.pitch_y < g.row_bytes(false) || g.pitch_c < g.row_bytes(true)) return fail_with_message(FUIFGPU_E_ARG, "yuv420: a row pitch smaller than the row");
+    g.frame_bytes = g.pitch_y * g.h + g.pitch_c * g.ch * (g.nv12 ? 1 : 2);
+    if (framerate) *framerate = y.framerate;
+    return FUIFGPU_OK;
+}
+}  // namespace fuifgpu
+
+// where plane p (0 Y, 1 Cb, 2 Cr; NV12: 1 = 2 = the plane of pairs) of a frame starts, and the bytes of a clip up to its last sample
+static int64_t yuv_plane_at(const fuifgpu::YuvGeom &g, int p) { return p == 0 ? 0 : g.pitch_y * g.h + (p == 2 && !g.nv12 ? g.pitch_c * g.ch : 0); }
+static int64_t yuv_clip_bytes(const fuifgpu::YuvGeom &g) {
+    return (g.nb_frames - 1) * g.frame_bytes + yuv_plane_at(g, 2) + (int64_t)(g.ch - 1) * g.pitch_c + g.row_bytes(true);
+}
+// the three channels as Image(w, h, maxval, 3) + read_YUV_file leave them, frames stacked (fuif.cpp:319-327); no samples yet
+static void yuv_image_shell(const fuifgpu::YuvGeom &g, int den, fuifgpu::Image &img) {
+    using namespace fuifgpu;
+    img.w = g.w; img.h = g.h * g.nb_frames; img.maxval = g.maxval; img.nb_channels = 3;
+    img.nb_frames = g.nb_frames; img.den = den;
+    img.ch.resize(3);
+    for (int c = 0; c < 3; c++) {
+        Chan &ch = img.ch[c];
+        ch.w = c ? g.cw : g.w; ch.h = (c ? g.ch : g.h) * g.nb_frames;
+        ch.hshift = ch.vshift = c ? 1 : 0;
+        ch.component = c; ch.minval = 0; ch.maxval = g.maxval;
+    }
+    img.transforms.push_back({TR_YCBCR, {}});
+    img.transforms.push_back({TR_SUBSAMPLE, {0}});   // 4:2:0
+    img.stale_tail = true;
+}
+// the host route: read_YUV_file's loops over memory; false: a sample above maxval
+static bool unpack_yuv_host(const uint8_t *src, const fuifgpu::YuvGeom &g, fuifgpu::Image &img) {
+    bool in_range = true;
+    for (int c = 0; c < 3; c++) {
+        fuifgpu::Chan &ch = img.ch[c];
+        const int pw = c ? g.cw : g.w, ph = c ? g.ch : g.h;
+        const int64_t pitch = c ? g.pitch_c : g.pitch_y, step = (int64_t)g.bytes * (c && g.nv12 ? 2 : 1), first = c == 2 && g.nv12 ? g.bytes : 0;
+        ch.data.resize((size_t)pw * ph * g.nb_frames);
+        int32_t *dst = ch.data.data();
+        for (int f = 0; f < g.nb_frames; f++)
+            for (int y = 0; y < ph; y++) {
+                const uint8_t *row = src + f * g.frame_bytes + yuv_plane_at(g, c) + y * pitch + first;
+                for (int x = 0; x < pw; x++) {
+                    int32_t v = row[x * step];
+                    if (g.bytes > 1) v += row[x * step + 1] << 8;
+                    in_range &= v <= g.maxval;
+                    *dst++ = v;
+                }
+            }
+    }
+    return in_range;
+}
+
+extern "C" int fuifgpu_quantization_constant_yuv(float quality, float chroma_quality, int squeeze_option, int chroma_table, int shift) {
+    Lossy l;
+    if (shift < 0 || !read_qualities(quality, chroma_quality, l)) return -FUIFGPU_E_ARG;
+    l.yuv = true;
+    return l.active ? quantization_constant(l, squeeze_option != 0, chroma_table != 0, shift) : 1;
+}
+
+extern "C" int fuifgpu_encode_yuv420(const void *const *frames, int on_device, int n, int w, int h, int bit_depth, const fuifgpu_yuv_options *yuv,
+                                     const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out) {
+    if (!frames || !blobs_out || !sizes_out || n < 1) return FUIFGPU_E_ARG;
+    for (int m = 0; m < n; m++) { blobs_out[m] = nullptr; sizes_out[m] = 0; }
+    fuifgpu_encode_options o;
+    Lossy l;
+    if (!read_encode_options(opt, o, on_device ? 1 : 0) || !read_lossy_options(lossy, l)) return FUIFGPU_E_ARG;
+    l.yuv = true;
+    YuvGeom g;
+    int framerate = 0;
+    if (const int rc = yuv_geometry(yuv, w, h, bit_depth, false, g, &framerate)) return rc;
+    if (o.max_properties < 0 || o.max_properties > 2 * kMaxRefs) return FUIFGPU_E_ARG;
+    if (o.max_tree_nodes < 1) o.max_tree_nodes = 4095;
+    if (o.max_tree_nodes > kMaxNodes) o.max_tree_nodes = kMaxNodes;
+    for (int m = 0; m < n; m++)
+        if (!frames[m]) return fail_with_message(FUIFGPU_E_ARG, "yuv420: a NULL frame");
+    const bool on_gpu = on_device != 0 || o.gpu_forward != 0;
+    const int den = framerate > 0 ? framerate : 10;   // fuif.cpp:335; image.h: den = 10
+    g_plane_h2d = g_plane_d2h = 0;
+    std::vector<Image> imgs((size_t)n);
+    std::vector<char> squeezed((size_t)n, 0);
+    auto release = [&]() { for (Image &im : imgs) for (Chan &c : im.ch) { if (c.dev) fuifgpu_dev_free(c.dev); c.dev = nullptr; } };
+    int rc = FUIFGPU_OK;
+    bool in_range = true;
+    for (Image &im : imgs) yuv_image_shell(g, den, im);
+    if (!on_gpu) {
+        for (int m = 0; m < n; m++) in_range &= unpack_yuv_host(static_cast<const uint8_t *>(frames[m]), g, imgs[(size_t)m]);
+    } else {
+        // the raw frames go to the device as they are (or are there already), ONE launch unpacks every plane of every frame of the call
+        // into the channels' own buffers, and the staging copies go
+        std::vector<YuvJob> jobs((size_t)n);
+        std::vector<void *> staged;
+        const size_t clip_bytes = (size_t)yuv_clip_bytes(g);
+        for (int m = 0; m < n && rc == FUIFGPU_OK; m++) {
+            YuvJob &job = jobs[(size_t)m];
+            job.src = static_cast<const uint8_t *>(frames[m]);
+            if (!on_device) {
+                void *dev = fuifgpu_dev_alloc(clip_bytes);
+                if (!dev) { rc = FUIFGPU_E_HIP; break; }
+                staged.push_back(dev);
+                g_plane_h2d += clip_bytes;
+                rc = fuifgpu_dev_upload(dev, frames[m], clip_bytes);
+                job.src = static_cast<const uint8_t *>(dev);
+            }
+            for (int c = 0; c < 3 && rc == FUIFGPU_OK; c++) {
+                Chan &ch = imgs[(size_t)m].ch[c];
+                ch.dev = (int32_t *)fuifgpu_dev_alloc(sizeof(int32_t) * (size_t)ch.w * ch.h);
+                if (!ch.dev) rc = FUIFGPU_E_HIP;
+                job.out[c] = ch.dev;
+            }
+        }
+        int flag = 0;
+        if (rc == FUIFGPU_OK) rc = unpack_yuv420_gpu(jobs.data(), n, g, &flag);   // (synchronous: the staging copies can go)
+        for (void *p : staged) fuifgpu_dev_free(p);
+        in_range = flag == 0;
+    }
+    if (rc == FUIFGPU_OK && !in_range) rc = fail_with_message(FUIFGPU_E_ARG, "yuv420: a sample above 2^bit_depth - 1");
+    for (int m = 0; m < n && rc == FUIFGPU_OK; m++) {
+        bool sq = false;
+        rc = squeeze_quantize_and_fetch(imgs[(size_t)m], o, l, true, on_gpu, on_device != 0, sq, rc);
+        squeezed[(size_t)m] = sq ? 1 : 0;
+    }
+    if (rc != FUIFGPU_OK) { release(); return rc; }
+    // pictures in device memory stay there until their last coded byte: the batch writer; so does a batch whose pixel loops run on the
+    // GPU (one launch pair for all of them); else picture by picture through the stream writer of fuifgpu_encode_image
+    if (on_device || (o.gpu_entropy && n > 1)) rc = write_streams_batch(imgs, 3, bit_depth, squeezed, o, blobs_out, sizes_out);
+    else for (int m = 0; m < n && rc == FUIFGPU_OK; m++) rc = write_stream(imgs[(size_t)m], 3, bit_depth, squeezed[(size_t)m] != 0, o, &blobs_out[m], &sizes_out[m]);
+    if (rc != FUIFGPU_OK) {
+        release();
+        for (int m = 0; m < n; m++) { free(blobs_out[m]); blobs_out[m] = nullptr; sizes_out[m] = 0; }
+    }
+    return rc;
 }

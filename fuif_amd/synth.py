@@ -102,6 +102,56 @@ def from_recipe(recipe):
     return (img // k * k).astype(np.int32)
 
 
+YUV_GUARD = 0xA5   # what yuv420_frame puts into the padding bytes of a pitched frame
+
+
+def yuv420_planes(w, h, bits=8, seed=1):
+    """the samples of yuv420_frame: (Y (h,w), Cb, Cr ((h+1)//2, (w+1)//2)) int32 -- smooth luma plus noise (photographic()'s first
+    channel), chroma in the middle third of the range (smooth, a little noise)"""
+    maxval = (1 << bits) - 1
+    luma = photographic(w, h, 1, bits, seed=seed)[0]
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    rng = np.random.default_rng(seed + 7919)
+    x = np.arange(cw, dtype=np.float64)[None, :] / cw
+    y = np.arange(ch, dtype=np.float64)[:, None] / ch
+    third = (maxval + 1) / 3.0
+    chroma = []
+    for _ in range(2):
+        fx, fy = rng.uniform(0.5, 3.0, size=2)
+        p1, p2 = rng.uniform(0, 2 * np.pi, size=2)
+        acc = 1.5 * third + 0.4 * third * np.sin(2 * np.pi * fx * x + p1) * np.cos(2 * np.pi * fy * y + p2) + rng.normal(0.0, third / 80.0, size=(ch, cw))
+        chroma.append(np.clip(np.rint(acc), np.ceil(third), np.floor(2 * third)).astype(np.int32))
+    return luma, chroma[0], chroma[1]
+
+
+def yuv420_frame(w, h, bits=8, seed=1, layout="i420", pitch=None):
+    """A seeded raw YUV 4:2:0 frame as bytes, what `fuif -y WxH[:bits]` reads: the Y plane, then Cb and Cr (layout "i420") or one plane of
+    Cb, Cr pairs ("nv12", the same samples); one byte per sample up to 8 bits, two little-endian above.  pitch: None = tight rows, else
+    (pitch_y, pitch_c) in bytes -- the padding behind every row but the frame's last is filled with YUV_GUARD."""
+    luma, cb, cr = yuv420_planes(w, h, bits, seed)
+    dt = np.uint8 if bits <= 8 else np.dtype("<u2")
+    planes = [luma, cb, cr] if layout == "i420" else [luma, np.stack([cb, cr], axis=-1).reshape(cb.shape[0], -1)]
+    out = []
+    for k, p in enumerate(planes):
+        rows = np.ascontiguousarray(p.astype(dt)).view(np.uint8).reshape(p.shape[0], -1)
+        want = rows.shape[1] if pitch is None else pitch[0 if k == 0 else 1]
+        if want < rows.shape[1]:
+            raise ValueError("a pitch smaller than the row")
+        padded = np.full((rows.shape[0], want), YUV_GUARD, np.uint8)
+        padded[:, : rows.shape[1]] = rows
+        out.append(padded.reshape(-1))
+    raw = np.concatenate(out)
+    last_row = planes[-1].shape[1] * np.dtype(dt).itemsize
+    tail = (0 if pitch is None else pitch[1]) - last_row
+    return raw[: raw.size - tail].tobytes() if pitch is not None and tail > 0 else raw.tobytes()
+
+
+def write_yuv(path, frame_bytes):
+    """a raw .yuv file for the reference's import/read_yuv.h (tight I420 frames only)"""
+    with open(path, "wb") as f:
+        f.write(frame_bytes)
+
+
 def write_pnm(path, planes, maxval=255):
     """planes: (C,H,W) int32 -> P5/P6/P7 file readable by the reference's import/read_pam.h."""
     c, h, w = planes.shape

@@ -439,6 +439,51 @@ int fuifgpu_encode_animations(const int32_t *const *frames, int on_device, int n
 /* the transform alone on raw device planes: n_planes (1..8) planes of a w x h strip of nb_frames (>= 2, dividing h) frames; match_dev
  * (w * h int32) gets the match channel, and the planes are modified IN PLACE (matched samples become 0).  Asynchronous on stream */
 int fuifgpu_fwd_match_frames(const int32_t *const *planes_dev, int n_planes, int w, int h, int nb_frames, int32_t *match_dev, void *stream);
+/* ---- YUV 4:2:0 video frames: what `fuif -y WxH[:b] in.yuv out.fuif` writes (import/read_yuv.h:29-63, fuif.cpp:277-283, 431-435) ----
+ * A frame is three planes of raw samples: Y (w x h), then Cb and Cr ((w+1)/2 x (h+1)/2 each), one byte per sample at 8 bits, two bytes
+ * little-endian above -- the planar form of a .yuv file, or as a hardware video decoder leaves a frame in device memory: planar (I420) or
+ * with the chroma samples interleaved (NV12, P010-like with the value in the LOW bits), often with a row pitch.
+ * The stream has three channels of UNEQUAL geometry (chroma: hshift = vshift = 1, hcshift = vcshift = 0) and its transform list starts
+ * [YCbCr, ChromaSubsample{0}]: both are only recorded, nothing is computed, the colour transform and the palettes are skipped
+ * (image_type == 2).  Default Squeeze runs if the option is on and luma has more than 20 samples (fuif.cpp:453); as the second channel is
+ * not luma-sized it has no chroma-first steps (transform/squeeze.h:276), every step covers the three channels, each with its own size.
+ * A quality quantises as for PNM input, components 1 and 2 with the chroma table, but with the luma factor times 3.0 and the quality
+ * factor over 3.0 (fuif.cpp:432-434) -- fuifgpu_quantization_constant_yuv.  Predictors and everything behind are those of PNM input.
+ * nb_frames > 1 writes "FUAF" with the frames stacked per channel (fuif.cpp:309-329) and NO Matching transform: there is no
+ * match_previous field, because the reference's previous-frame matcher indexes every channel with luma coordinates
+ * (transform/2dmatch.h:321-322) and runs off the end of the chroma planes -- `-M 0` is the only setting of the CLI that works for .yuv
+ * clips, and there are no bytes to reproduce for any other.  A clip needs an even h: otherwise the stacked chroma height is not the
+ * (H+1)/2 of the strip the decoder expects. */
+typedef struct {
+    uint32_t struct_size;   /* = sizeof(fuifgpu_yuv_options) of the CALLER's header, versioned like fuifgpu_encode_options: fields the caller's
+                               struct ends before are 0 (nb_frames: 1); 0 or a size that is not a multiple of 4 is FUIFGPU_E_ARG */
+    int32_t layout;         /* 0 = I420 (Y plane, Cb plane, Cr plane), 1 = NV12 / P0xx (Y plane, then one plane of Cb, Cr pairs); else FUIFGPU_E_ARG */
+    int32_t pitch_y;        /* bytes from one luma row to the next, 0 = tight; smaller than a row: FUIFGPU_E_ARG */
+    int32_t pitch_c;        /* the same for the chroma planes (NV12: for the interleaved plane) */
+    int32_t nb_frames;      /* 1 or more (below 1, or above 65535: FUIFGPU_E_ARG; a struct that ends before the field: 1): frames back to back,
+                               each pitch_y * h + pitch_c * ((h+1)/2) * (I420: 2, NV12: 1) bytes; the last row of the last plane may end
+                               with its samples */
+    int32_t framerate;      /* as in fuifgpu_animation_options */
+} fuifgpu_yuv_options;
+/* n pictures (or clips) of one shape: frames[m] points at picture m's raw bytes, in host memory or (on_device != 0) in memory of the
+ * current device, which is read and never written.  bit_depth 8..14.  yuv NULL = tight I420, one frame.  opt->ycocg is ignored; lossy as
+ * for fuifgpu_encode_image_lossy.  A sample above 2^bit_depth - 1 in a 16-bit container is FUIFGPU_E_ARG on every route (the reference
+ * would wrap it into its int16 sample).  With tree_mode 0 the bytes are those of
+ * `fuif -I 0 -K 0 -X 0 -Y 0 -y WxH[:b] [-Q ..] [-R 0] [-M 0 [-F r]]`.  Host memory with opt->gpu_forward == 0: unpacked by the reference's
+ * loops, every picture through the stream writer of fuifgpu_encode_image.  gpu_forward: the RAW frames go to the device (1.5 or 3 bytes
+ * per pixel, what fuifgpu_encode_plane_traffic then reports), fuifgpu_unpack_yuv420's kernel unpacks all of them in one launch and the
+ * forward Squeeze / Quantize kernels run per channel.  on_device: the same on the caller's memory, and the channels stay on the device
+ * until the last coded byte, through the batch writer like fuifgpu_encode_images_device.  An error leaves every blobs_out[m] NULL.
+ * Found by symbol lookup, like the two entry points below it: the ABI version does not change. */
+int fuifgpu_encode_yuv420(const void *const *frames, int on_device, int n, int w, int h, int bit_depth, const fuifgpu_yuv_options *yuv,
+                          const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out);
+/* the unpacking alone on raw device memory: one frame (yuv->nb_frames is not looked at) -> three tight int32 planes, y_out w x h, cb_out
+ * and cr_out (w+1)/2 x (h+1)/2.  Asynchronous on stream.  flag_device (may be NULL): one word of device memory that is set to a non-zero
+ * value if any sample exceeds 2^bit_depth - 1, and is not written otherwise.  w * h == 0 touches nothing. */
+int fuifgpu_unpack_yuv420(const void *frame_device, int w, int h, int bit_depth, const fuifgpu_yuv_options *yuv, int32_t *y_out, int32_t *cb_out,
+                          int32_t *cr_out, int32_t *flag_device, void *stream);
+/* fuifgpu_quantization_constant for `-y` input: the same tables behind the two factors of fuif.cpp:432-434 */
+int fuifgpu_quantization_constant_yuv(float quality, float chroma_quality, int squeeze_option, int chroma_table, int shift);
 /* host: the constant fuif.cpp:459-503 gives one channel -- squeeze_option = opt->squeeze (the OPTION, not whether the picture was large
  * enough to be squeezed), chroma_table = 1 for the chroma table, shift = hcshift + vcshift (capped at 15).  1 when both qualities are
  * >= 100.  A negative shift or a quality the entry points above refuse gives -FUIFGPU_E_ARG. */
