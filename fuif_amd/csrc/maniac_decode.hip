@@ -1835,12 +1835,12 @@ __global__ __launch_bounds__(64) FUIF_OCCUPANCY void k_maniac_decode(DecodeParam
                                     switch (predictor) {  // context_predict.h:157-166
                                         case 0: guess = zero; break;
                                         case 1: guess = (l + top) / 2; break;
-                                        case 2: guess = median3(l + top - topleft, l, top); break;
+                                        case 2: guess = median3((int16_t)(l + top - topleft), l, top); break;   // the gradient narrowed to pixel_type (:160; one v_bfe_i32), property 6 is not
                                         case 3: guess = l; break;
                                         case 4: guess = top; break;
                                         case 5: guess = (l + topleft + top + topright) / 4; break;
                                         case 6: { int t = l + top - topleft; guess = t < minv ? minv : (t > maxv ? maxv : t); break; }
-                                        default: guess = median3(l + top - topleft, l, top); break;
+                                        default: guess = median3((int16_t)(l + top - topleft), l, top); break;
                                     }
                                 }
                                 const int mn = minv - guess, mx = maxv - guess;

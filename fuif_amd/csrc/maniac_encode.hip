@@ -98,7 +98,7 @@ DEV int enc_props_and_guess(const EncGroup &g, int64_t i, int32_t *p) {
         case 4: return top;
         case 5: return (left + topleft + top + topright) / 4;
         case 6: { const int t = left + top - topleft; return t < g.minval ? g.minval : (t > g.maxval ? g.maxval : t); }
-        default: return e_median3(left + top - topleft, left, top);
+        default: return e_median3((int16_t)(left + top - topleft), left, top);   // :160,165 narrow the gradient to pixel_type (the property above stays an int)
     }
 }
 DEV void enc_model_pixel(const EncGroup &g, const EncNode *tree, int n_nodes, int64_t i, int32_t *guess_out, int32_t *leaf_out) {

@@ -630,12 +630,12 @@ inline int props_and_guess(int32_t *p, const Chan &c, const std::vector<RefInfo>
     switch (predictor) {
         case 0: return c.zero;
         case 1: return (left + top) / 2;
-        case 2: return median3(left + top - topleft, left, top);
+        case 2: return median3((int16_t)(left + top - topleft), left, top);   // :160 narrows the gradient to pixel_type (the property above stays an int)
         case 3: return left;
         case 4: return top;
         case 5: return (left + topleft + top + topright) / 4;
         case 6: { int t = left + top - topleft; return t < c.minval ? c.minval : (t > c.maxval ? c.maxval : t); }
-        default: return median3(left + top - topleft, left, top);
+        default: return median3((int16_t)(left + top - topleft), left, top);
     }
 }
 

@@ -204,6 +204,95 @@ def jpeg_like_wrapping(bw, bh, seed, bit_depth=10, squeeze=1):
     return encode_channels(chans, bw * 8, bh * 8, 1, bit_depth, [TR_DCT, 0, TR_QUANTIZE, 0], squeeze=squeeze)
 
 
+def blocks_15bit(w, h, seed=7701):
+    """(1, h, w): 8x8 blocks, each one of {0, 1000, 20000, 30000, 32767} (seeded), and every fifth sample of the main diagonal large.
+    At the corners where three different blocks meet, left + top - topleft leaves int16 with left != top: the median predictor's
+    first argument, which the reference narrows to pixel_type (context_predict.h:160,165).  Flat blocks compress, so an encoder keeps
+    the group compressed -- random 15-bit data is rolled back to the uncompressed form, which uses no predictor."""
+    levels = np.array([0, 1000, 20000, 30000, 32767], np.int32)
+    pick = np.random.default_rng(seed).integers(0, 5, ((h + 7) // 8, (w + 7) // 8))
+    img = np.kron(levels[pick], np.ones((8, 8), np.int32))[:h, :w].copy()
+    for i in range(0, min(w, h), 5):
+        img[i, i] = 32767 - (i * 37) % 500
+    return img[None].astype(np.int32)
+
+
+def quadrants_15bit(w, h):
+    """(1, h, w) gray: four flat quadrants 0 | 20000 over 30000 | 32767.  Squeeze keeps flat quadrants flat, so the averages that are left
+    after every Squeeze step meet in the same corner: 30000 + 20000 - 0 = 50 000 in the one median-predicted channel, which stays compressed"""
+    img = np.zeros((1, h, w), np.int32)
+    img[0, : h // 2, w // 2:], img[0, h // 2:, : w // 2], img[0, h // 2:, w // 2:] = 20000, 30000, 32767
+    return img
+
+
+def quadrants_14bit(w, h):
+    """(3, h, w) RGB: four flat quadrants whose Co plane (R - B, -16383..16383 after YCoCg) steps from -16383 to 9000 to 16383: at the
+    centre left + top - topleft = 16383 + 9000 + 16383 = 41 766 on the Co plane of a picture of only 14 bits"""
+    img = np.empty((3, h, w), np.int32)
+    img[1] = 8000
+    hy, hx = h // 2, w // 2
+    for (ys, xs), (r, b) in zip(((slice(0, hy), slice(0, hx)), (slice(0, hy), slice(hx, w)), (slice(hy, h), slice(0, hx)), (slice(hy, h), slice(hx, w))),
+                                ((0, 16383), (9000, 0), (16383, 0), (12000, 3000))):
+        img[0][ys, xs], img[2][ys, xs] = r, b
+    return img
+
+
+def gradient_wraps(plane, zero=0):
+    """samples of a coded plane at which left + top - topleft is outside int16 and left != top, with the neighbour rules of
+    context_predict.h:126-128: where the median of the narrowed gradient is not the median of the int gradient"""
+    p = np.asarray(plane, np.int64)
+    left = np.concatenate([np.full((p.shape[0], 1), zero, np.int64), p[:, :-1]], axis=1)
+    top = np.concatenate([np.full((1, p.shape[1]), zero, np.int64), p[:-1]], axis=0)
+    topleft = np.concatenate([np.full((1, p.shape[1]), zero, np.int64), left[:-1]], axis=0)
+    topleft[0] = left[0]          # y == 0: topleft = left
+    topleft[1:, 0] = left[1:, 0]  # x == 0: topleft = left
+    g = left + top - topleft
+    return int((((g > 32767) | (g < -32768)) & (left != top)).sum())
+
+
+# the golden fixtures (tests/golden/make_golden.py) whose manifest entry records `gradient_wraps`
+WRAP_FIXTURES = ("grad16_gray15_48x64_nosqueeze", "grad16_gray15_quadrants_48x64", "grad16_rgb14_quadrants_24x40_nosqueeze",
+                 "grad16_rgb14_quadrants_24x40_cli_I0")
+
+
+def group_headers(blob, port):
+    """([(first channel, channels - 1, predictor, compress)], the oracle's Decoded before undo_transforms): a channel group starts with
+    the big-endian varint count << 4 | predictor << 1 | compress (encoding.cpp:77,266-268), at the positions the oracle's parse recorded
+    (port: oracle_py.Port)"""
+    d = port.decode(blob, undo=False)
+    out = []
+    for first, pos in d.groups:
+        v = 0
+        while True:
+            b = blob[pos]
+            pos += 1
+            v = (v << 7) | (b & 127)
+            if b < 128:
+                break
+        out.append((first, v >> 4, (v >> 1) & 7, v & 1))
+    return out, d
+
+
+def count_gradient_wraps(blob, port, coded=None):
+    """gradient_wraps summed over the compressed groups with the median predictor (2, or 7 = the `default:` branch), on the coded planes
+    of `coded` (a Decoded before undo_transforms, e.g. the real reference's; default: the oracle's own)"""
+    groups, d = group_headers(blob, port)
+    coded = coded or d
+    n = 0
+    for first, more, predictor, compress in groups:
+        if compress and predictor in (2, 7):
+            n += sum(gradient_wraps(coded.channels[c]["data"], coded.channels[c]["zero"]) for c in range(first, first + more + 1) if coded.channels[c]["size"])
+    return n
+
+
+def predicted_blocks(w, h):
+    """one untransformed 15-bit channel of blocks_15bit through the writer, which gives a picture channel the median predictor: the
+    group stays compressed, so the predictor really runs (tests/test_predictors_and_groups.py asserts the header's compress bit)"""
+    c = _picture_channels(w, h, 1)[0]
+    c["data"] = blocks_15bit(w, h)[0]
+    return encode_channels([c], w, h, 1, 14, [])   # (the writer's headers stop at 14 bits; the coded range is the data's, 0..32767)
+
+
 # `ycocg` / `dct`: the planner switches that apply to the case (FUIFGPU_FUSE_YCOCG; FUIFGPU_FUSE_DEQUANT).
 # The comment beside a wrapping case = post-transform samples on which the int32 inverse chain (the oracle before the int16 stores were
 # matched) differed from the real reference, of the case's post-transform samples.
@@ -225,6 +314,9 @@ CASES = [
     dict(name="soft_match_chain_33x50", make=soft_match, args=dict(w=33, h=50, amp=0, seed=7602, chain=True), wraps=True),                      # 1139 of 1650 (69.0 %)
     dict(name="jpeg_like_wrapping_12x10_blocks", make=jpeg_like_wrapping, args=dict(bw=12, bh=10, seed=7401), wraps=True, dct=True),         # 3972 of 7680 (51.7 %)
     dict(name="jpeg_like_wrapping_6x5_blocks_dc_coded", make=jpeg_like_wrapping, args=dict(bw=6, bh=5, seed=7402, squeeze=0), wraps=True, dct=True),  # 1236 of 1920 (64.4 %)
+    # no transform at all: the narrowing is in the entropy stage, the median predictor's gradient (context_predict.h:160); 70x45 = one 64-pixel chunk + 6
+    # (a decoder that takes the median of the int gradient loses the stream at the first such sample: every sample behind it differs)
+    dict(name="predicted_blocks_15bit_70x45", make=predicted_blocks, args=dict(w=70, h=45), wraps=True),
 ]
 
 

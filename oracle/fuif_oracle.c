@@ -695,12 +695,12 @@ static inline int predict_and_properties(int32_t *p, const fo_channel *ch, int x
     switch (predictor) {
         case 0: return ch->zero;
         case 1: return (left + top) / 2;
-        case 2: return median3(left + top - topleft, left, top);
+        case 2: return median3(px(left + top - topleft), left, top);   /* :160 median3((pixel_type)(left+top-topleft), ...): the gradient is narrowed, property 6 above is not */
         case 3: return left;
         case 4: return top;
         case 5: return (left + topleft + top + topright) / 4;
         case 6: return CLAMPI(left + top - topleft, ch->minval, ch->maxval);
-        default: return median3(left + top - topleft, left, top);
+        default: return median3(px(left + top - topleft), left, top);
     }
 }
 

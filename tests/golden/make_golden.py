@@ -22,6 +22,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+from fuif_amd import edgecases  # noqa: E402
 from fuif_amd.synth import graphic, photographic, write_pnm  # noqa: E402
 from oracle_py import Ref, run_ref_cli  # noqa: E402
 
@@ -133,9 +134,60 @@ SOFTMATCH_SPECS = [
     ("softmatch_rgb_graphic_nosqueeze_72x60", dict(w=72, h=60, channels=3, bits=8, seed=53, colors=300), dict(softmatch=1, match_distance=200, squeeze=0)),
     ("softmatch_anim4_40x28_q2", dict(w=40, h=28, channels=3, bits=8, seed=710, static=True), dict(softmatch=1, match_distance=-2, frames=4, quant=2)),
 ]
-PREVIEWS = {"yuv420p_97x61": [1, 3], "softmatch_rgb_graphic_96x80_q3": [2], "c1_rgb8_512x512": [0, 1, 2, 3, 4], "rgb8_97x61": [0, 2, 4], "jpeg420_256x192_q90": [0, 1, 2, 3, 4],
+# Predictors 1, 4..7 (the CLI's defaults only ever write 0, 2 and 3), channel groups of more than one channel (-G; with Squeeze the CLI's default
+# is one channel per group) and the median predictor's gradient beyond int16.  `-P` takes one digit per channel, the last digit for every later
+# channel (fuif.cpp:136, encoding.cpp:503).  Regenerate with GOLDEN_ONLY=<these names> only.
+#   picture: a hand-made input instead of photographic() -- "outlier" (here), or a function of fuif_amd/edgecases.py
+#   const_channel: (channel, value): that channel made flat, so that a group holds a channel with minval == maxval in front of real ones
+#   flags as a dict(library=True, ...): encoded through the reference's library calls (oracle/ref_driver.cpp fuifref_encode), which is how a
+#   15-bit picture reaches the reference encoder
+P_RGB_65 = dict(w=65, h=34, channels=3, bits=8, seed=91)      # 65 = one 64-pixel chunk of the entropy kernel + one pixel
+P_RGB_97 = dict(w=97, h=61, channels=3, bits=8, seed=92)
+# The reference encoder groups channels only between two preview sizes it has found (encoding.cpp:516, image.cpp:124-135), and only neighbours of
+# one size (:519).  Without Squeeze it finds none, and on an RGB picture that needs four Squeeze steps (more than 64 samples a side: 97x61) none
+# either, because the chroma planes are one step ahead of the luma plane (squeeze.h:277-292): -G changes nothing there.  With three steps
+# (33..64 a side) the chroma averages sit at 1:16, and the two chroma residuals of every later step make a group of two; three neighbours
+# of one size do not occur with the default Squeeze parameters, so -G 3 groups like -G 2.
+P_RGB_61 = dict(w=61, h=47, channels=3, bits=8, seed=94)
+P_RGBA14 = dict(w=40, h=36, channels=4, bits=14, seed=93)
+NO_PALETTE = ["-K", "0", "-X", "0", "-Y", "0"]
+PREDICTOR_SPECS = [("rgb8_65x34_P%d_nosqueeze" % p, P_RGB_65, ["-P", str(p), "-R", "0"]) for p in (1, 4, 5, 6, 7)] + [
+    # w = 1: left = zero, topleft = left, topright = top on every row; h = 1: the single-row rules
+    # ("outlier": flat 10 with one sample of 250 in the middle -- a ramp of nine samples is rolled back to the uncompressed form, which uses no
+    # predictor; the four samples of 2x2 always are: uncompressed they cost 4 * 8 + 16 bits (encoding.cpp:531-545), so 2x7, the smallest
+    # two-column picture of this kind whose group stays compressed, stands beside it)
+    ("gray8_1x9_P541_nosqueeze", dict(w=1, h=9, channels=1, bits=8, picture="outlier"), ["-P", "541", "-R", "0"] + NO_PALETTE),
+    ("gray8_9x1_P541_nosqueeze", dict(w=9, h=1, channels=1, bits=8, picture="outlier"), ["-P", "541", "-R", "0"] + NO_PALETTE),
+    ("gray8_2x2_P541_nosqueeze", dict(w=2, h=2, channels=1, bits=8, picture="outlier"), ["-P", "541", "-R", "0"] + NO_PALETTE),
+    ("gray8_2x7_P541_nosqueeze", dict(w=2, h=7, channels=1, bits=8, picture="outlier"), ["-P", "541", "-R", "0"] + NO_PALETTE),
+    # non-zero predictors on (negative) Squeeze residuals: /2 and /4 truncate toward zero, the magnitude bound is maxval - minval
+    ("rgb8_97x61_P1", P_RGB_97, ["-P", "1"]),
+    ("rgb8_97x61_P5", P_RGB_97, ["-P", "5"]),
+    ("rgb8_97x61_P2461", P_RGB_97, ["-P", "2461"]),
+    ("rgba14_40x36_P6", P_RGBA14, ["-P", "6"] + NO_PALETTE),
+    ("rgba14_40x36_P1", P_RGBA14, ["-P", "1"] + NO_PALETTE),
+    ("rgb8_65x34_E24_P5", P_RGB_65, ["-E", "24", "-P", "5"]),
+    ("rgb8_61x47_G2", P_RGB_61, ["-G", "2"]),
+    # (-G 3 on this picture writes the bytes of -G 2: no three neighbours of one size)
+    # no colour transform and a flat second channel: its Squeeze residuals are all 0, so every group of two starts with a channel whose
+    # minval == maxval (filled without a symbol, encoding.cpp:300-303) in front of a coded one
+    ("rgb8_61x47_G3_flat_second_channel", dict(P_RGB_61, const_channel=(1, 77)), ["-G", "3", "-C", "0"] + NO_PALETTE),
+    ("rgb8_61x47_G2_P5", P_RGB_61, ["-G", "2", "-P", "5"]),
+    # gray + alpha: no chroma planes that run a Squeeze step ahead, so the encoder finds every preview size (image.cpp:124-135) -- previews cut the
+    # stream at several places, and every Squeeze step leaves two residuals of one size: groups of two throughout
+    ("ga8_70x66_G2_P5", dict(w=70, h=66, channels=2, bits=8, seed=97), ["-G", "2", "-P", "5"] + NO_PALETTE),
+    # left + top - topleft beyond int16 with left != top: the median predictor takes (pixel_type)(left+top-topleft) (context_predict.h:160,165)
+    ("grad16_gray15_48x64_nosqueeze", dict(w=48, h=64, channels=1, bits=15, picture="blocks_15bit"), dict(library=True, colorspace=0, squeeze=0)),
+    # (with Squeeze the 6x8 averages of the blocks picture are rolled back to the uncompressed form; flat quadrants stay compressed)
+    ("grad16_gray15_quadrants_48x64", dict(w=48, h=64, channels=1, bits=15, picture="quadrants_15bit"), dict(library=True, colorspace=0, squeeze=1)),
+    ("grad16_rgb14_quadrants_24x40_nosqueeze", dict(w=24, h=40, channels=3, bits=14, picture="quadrants_14bit"), dict(library=True, squeeze=0)),
+    # what the product's writer has to reproduce byte for byte with tree_mode 0 (tests/test_predictors_and_groups.py)
+    ("grad16_rgb14_quadrants_24x40_cli_I0", dict(w=24, h=40, channels=3, bits=14, picture="quadrants_14bit"), ["-I", "0", "-R", "0"] + NO_PALETTE),
+]
+# (ga8_70x66_G2_P5: a Squeeze + -P stream on which previews 3 and 4 cut behind compressed predictor-5 groups)
+PREVIEWS = {"ga8_70x66_G2_P5": [3, 4], "yuv420p_97x61": [1, 3], "softmatch_rgb_graphic_96x80_q3": [2], "c1_rgb8_512x512": [0, 1, 2, 3, 4], "rgb8_97x61": [0, 2, 4], "jpeg420_256x192_q90": [0, 1, 2, 3, 4],
             "pal_rgb_graphic_120x90": [1, 3], "approx_rgb8_96x80_A3": [2], "approx_quant_rgb8_40x30": [3], "match_rgb_graphic_96x80": [3]}
-TRUNCATE_EXTRA = {"softmatch_rgb_graphic_nosqueeze_72x60": [0.7], "softmatch_anim4_40x28_q2": [0.6], "approx_on_palette_gray12_24x50": [0.8], "match_rgb_graphic_96x80": [0.6]}
+TRUNCATE_EXTRA = {"rgb8_97x61_P5": [0.5], "rgb8_61x47_G2_P5": [0.6], "softmatch_rgb_graphic_nosqueeze_72x60": [0.7], "softmatch_anim4_40x28_q2": [0.6], "approx_on_palette_gray12_24x50": [0.8], "match_rgb_graphic_96x80": [0.6]}
 TRUNCATE = {"yuv420p_75x49_Q60": [0.6], "rgb8_512x384_I16_bigtrees": [0.8], "permute_channel_rgb8_48x40": [0.5], "permute_explicit_rgb8_48x40": [0.6], "rgb8_97x61": [0.2, 0.55, 0.93], "rgb8_128x128_I0": [0.5], "rgb8_112x96_E18": [0.7], "rgb8_120x88_E50": [0.6], "jpeg420_256x192_q90": [0.4], "rgb8_64x64_U": [0.6],
             "pal_rgba_graphic_72x64": [0.5], "pal_rgb_sparse_128x96": [0.7],
             "gray8_nosqueeze_60x40": [0.6], "rgb8_96x96_nosqueeze": [0.45]}
@@ -152,12 +204,19 @@ def main():
             manifest = json.load(f)
         manifest["fixtures"] = [e for e in manifest["fixtures"] if e["name"] not in only]
     tmp = tempfile.mkdtemp()
-    for name, gen, flags in SPECS + GRAPHIC_SPECS + [(n, g, j) for n, g, j in JPEG_SPECS] + YUV_SPECS + ANIM_SPECS + PERMUTE_SPECS + SOFTMATCH_SPECS:
+    for name, gen, flags in SPECS + GRAPHIC_SPECS + [(n, g, j) for n, g, j in JPEG_SPECS] + YUV_SPECS + ANIM_SPECS + PERMUTE_SPECS + SOFTMATCH_SPECS + PREDICTOR_SPECS:
         if only and name not in only:
             continue
         gen = dict(gen)
+        source = dict(gen) if "picture" in gen or "const_channel" in gen else gen
         static = gen.pop("static", False)
-        if "colors" in gen:
+        picture, const_channel = gen.pop("picture", None), gen.pop("const_channel", None)
+        if picture == "outlier":
+            img = np.full((gen["channels"], gen["h"], gen["w"]), 10, np.int32)
+            img.reshape(gen["channels"], -1)[:, gen["w"] * gen["h"] // 2] = 250
+        elif picture:
+            img = getattr(edgecases, picture)(gen["w"], gen["h"])
+        elif "colors" in gen:
             img = graphic(**gen)
         else:
             gen.pop("photographic", None)
@@ -167,7 +226,14 @@ def main():
                 img = img // poster * poster   # more than 256 colours, sparse per-channel histograms
         maxval = (1 << gen["bits"]) - 1
         out = os.path.join(HERE, name + ".fuif")
-        if isinstance(flags, dict) and ("permute" in flags or "softmatch" in flags):
+        if const_channel:
+            img[const_channel[0]] = const_channel[1]
+        if isinstance(flags, dict) and "library" in flags:
+            blob = ref.encode(img, maxval=maxval, **{k: v for k, v in flags.items() if k != "library"})
+            with open(out, "wb") as f:
+                f.write(blob)
+            src, cli_flags = None, []
+        elif isinstance(flags, dict) and ("permute" in flags or "softmatch" in flags):
             if flags.get("frames", 1) > 1:     # the vertical film strip of an animation whose frames share most pixels with the first one
                 strip = []
                 for i in range(flags["frames"]):
@@ -223,7 +289,7 @@ def main():
                 raise SystemExit("reference CLI failed for %s: %s %s" % (name, r.stdout[-400:], r.stderr[-400:]))
         blob = open(out, "rb").read()
         entry = {"name": name, "file": name + ".fuif", "bytes": len(blob), "file_sha256": hashlib.sha256(blob).hexdigest(),
-                 "source": gen, "cli_flags": cli_flags if not isinstance(flags, dict) else (["<library: oracle/ref_driver.cpp fuifref_encode>", json.dumps(flags)] if ("permute" in flags or "softmatch" in flags) else ["<stream written by fuif_amd/jpeglike.py; expected planes = the reference decoding it>", json.dumps(flags)] if "writer_factors" in flags else ["<jpeg/anim/yuv>", json.dumps(flags)] + cli_flags), "cases": []}
+                 "source": source, "cli_flags": cli_flags if not isinstance(flags, dict) else (["<library: oracle/ref_driver.cpp fuifref_encode>", json.dumps(flags)] if ("permute" in flags or "softmatch" in flags or "library" in flags) else ["<stream written by fuif_amd/jpeglike.py; expected planes = the reference decoding it>", json.dumps(flags)] if "writer_factors" in flags else ["<jpeg/anim/yuv>", json.dumps(flags)] + cli_flags), "cases": []}
         cases = [("full", -1, len(blob))]
         cases += [("preview%d" % k, k, len(blob)) for k in PREVIEWS.get(name, [])]
         cases += [("trunc%02d" % int(f * 100), -1, int(len(blob) * f)) for f in TRUNCATE.get(name, []) + TRUNCATE_EXTRA.get(name, [])]
@@ -232,13 +298,20 @@ def main():
             entry["cases"].append({"case": cname, "preview": preview, "nbytes": nbytes, "ok": bool(pre.ok),
                                    "info": pre.info, "transforms": pre.transforms, "pre": describe(pre), "post": describe(post)})
         # lossless fixtures must reproduce the source pixels
-        if (not isinstance(flags, dict) and "-Q" not in flags) or (isinstance(flags, dict) and "permute" in flags):
+        if (not isinstance(flags, dict) and "-Q" not in flags) or (isinstance(flags, dict) and ("permute" in flags or "library" in flags)):
             full = entry["cases"][0]
             _, post = ref.decode_both(blob)
             assert all(np.array_equal(post.channels[c]["data"], img[c]) for c in range(gen["channels"])), name
             full["lossless_roundtrip"] = True
+        if name in edgecases.WRAP_FIXTURES:
+            from oracle_py import Port
+            entry["gradient_wraps"] = edgecases.count_gradient_wraps(blob, Port(), ref.decode(blob, undo=False))
+            assert entry["gradient_wraps"] > 0, name
         manifest["fixtures"].append(entry)
         print("%-32s %7d bytes  %d cases  channels=%d" % (name, len(blob), len(entry["cases"]), entry["cases"][0]["info"]["nch"]))
+    # PREDICTOR_SPECS' entries in the order of the specs, behind every other entry, whichever GOLDEN_ONLY pass wrote them (a stable sort)
+    order = {n: i for i, (n, _, _) in enumerate(PREDICTOR_SPECS)}
+    manifest["fixtures"].sort(key=lambda e: order.get(e["name"], -1))
     with open(os.path.join(HERE, "manifest.json"), "w") as f:
         json.dump(manifest, f, indent=0, separators=(",", ":"))
     print("total fixture bytes:", sum(e["bytes"] for e in manifest["fixtures"]))

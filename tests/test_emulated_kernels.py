@@ -54,6 +54,8 @@ SELECTED = [
     ("tests/test_gpu_synthetic.py::test_unsqueeze_kernels_on_geometries_around_their_tile_edges", 80),
     ("tests/test_gpu_transform_exports.py", 25),
     ("tests/test_gpu_int16_edges.py", 30),
+    ("tests/test_predictors_and_groups.py::test_kernels_decode_every_new_fixture", 30),
+    ("tests/test_predictors_and_groups.py::test_writer_on_a_gradient_beyond_int16_gpu_routes", 10),
 ] + [("tests/test_gpu_parity.py::test_golden_fixtures_bit_exact[%d]" % k, 12) for k in range(8)] + [
     ("tests/test_gpu_group_parallel.py::test_jpeg_like_indexed", 10),
     ("tests/test_gpu_group_parallel.py::test_writer_indexed_streams_vs_oracle[97-61-3-8-2]", 8),
