@@ -172,6 +172,7 @@ ABI_SYMBOLS = [
     "fuifgpu_encode_image_ex", "fuifgpu_encode_images_ex", "fuifgpu_fwd_palette",
     "fuifgpu_encode_animation", "fuifgpu_encode_animations", "fuifgpu_fwd_match_frames",
     "fuifgpu_encode_yuv420", "fuifgpu_unpack_yuv420", "fuifgpu_quantization_constant_yuv",
+    "fuifgpu_plan_create_keep", "fuifgpu_plan_keep", "fuifgpu_plan_yuv420_bytes", "fuifgpu_batch_pack_yuv420", "fuifgpu_batch_download_yuv420", "fuifgpu_pack_yuv420",
     "fuifgpu_plane_checksums", "fuifgpu_device_count", "fuifgpu_set_device", "fuifgpu_get_device", "fuifgpu_batch_device", "fuifgpu_peer_copy", "fuifgpu_batch_set_in_flight",
 ]
 
@@ -283,6 +284,12 @@ def lib():
     L.fuifgpu_encode_yuv420.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(YuvOptions), C.POINTER(EncodeOptions), C.POINTER(LossyOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.fuifgpu_unpack_yuv420.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(YuvOptions), vp, vp, vp, vp, vp]
     L.fuifgpu_quantization_constant_yuv.argtypes = [C.c_float, C.c_float, C.c_int, C.c_int, C.c_int]
+    L.fuifgpu_plan_create_keep.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(vp)]
+    L.fuifgpu_plan_keep.argtypes = [vp, C.POINTER(C.c_int)]
+    L.fuifgpu_plan_yuv420_bytes.argtypes = [vp, C.POINTER(YuvOptions)]; L.fuifgpu_plan_yuv420_bytes.restype = C.c_size_t
+    L.fuifgpu_batch_pack_yuv420.argtypes = [vp, C.c_int, C.c_int, C.POINTER(YuvOptions), vp, C.c_int64, vp]
+    L.fuifgpu_batch_download_yuv420.argtypes = [vp, C.c_int, C.POINTER(YuvOptions), vp, vp]
+    L.fuifgpu_pack_yuv420.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(YuvOptions), vp, vp]
     L.fuifgpu_encode_plane_traffic.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.fuifgpu_quantization_constant.argtypes = [C.c_float, C.c_float, C.c_int, C.c_int, C.c_int]
     L.fuifgpu_encode_image.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
@@ -309,14 +316,30 @@ def _check(code):
 
 
 class Plan:
-    """Parsed header + channel table + inverse schedule of one stream (host only)."""
+    """Parsed header + channel table + inverse schedule of one stream (host only).  keep: transforms the schedule leaves standing
+    (fuifgpu_plan_create_keep, Image::undo_transforms(keep)); 2 on a `fuif -y` stream leaves Y, Cb, Cr as they were coded."""
 
-    def __init__(self, blob):
+    def __init__(self, blob, keep=0):
         L = lib()
         self._h = C.c_void_p()
-        _check(L.fuifgpu_plan_create(bytes(blob[:65536]) if len(blob) > 65536 else bytes(blob), min(len(blob), 65536), C.byref(self._h)))
+        head = bytes(blob[:65536]) if len(blob) > 65536 else bytes(blob)
+        if keep:
+            _check(L.fuifgpu_plan_create_keep(head, len(head), int(keep), C.byref(self._h)))
+        else:
+            _check(L.fuifgpu_plan_create(head, len(head), C.byref(self._h)))
         self.info = ImageInfo()
         _check(L.fuifgpu_plan_info(self._h, C.byref(self.info)))
+
+    @property
+    def keep(self):
+        k = C.c_int(0)
+        _check(lib().fuifgpu_plan_keep(self._h, C.byref(k)))
+        return k.value
+
+    def yuv420_bytes(self, layout="i420", pitch_y=0, pitch_c=0, nb_frames=1):
+        """bytes of one image's raw 4:2:0 frame(s) in that layout (fuifgpu_plan_yuv420_bytes); 0: this plan cannot be written as such"""
+        yuv = make_yuv_options(layout, pitch_y, pitch_c, nb_frames)
+        return int(lib().fuifgpu_plan_yuv420_bytes(self._h, C.byref(yuv)))
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
@@ -498,7 +521,24 @@ class Batch:
         n = self.n_loaded - first_image if n_images is None else n_images
         _check(lib().fuifgpu_batch_pack_out(self._h, first_image, n, components, dst_device_ptr, stream))
 
+    def pack_yuv420(self, first_image, n_images, dst_device_ptr, layout="i420", pitch_y=0, pitch_c=0, nb_frames=1, image_stride=0, stream=None):
+        """raw YUV 4:2:0 frames of images [first, first+n) of a keep = 2 batch into DEVICE memory, image_stride bytes apart (0 = tight,
+        plan.yuv420_bytes(...)), in one launch (fuifgpu_batch_pack_yuv420); call after undo_transforms().  nb_frames: 1 = the stacked strip
+        of a clip, the stream's frame count = its frames back to back, the layout encode_yuv420_clip reads"""
+        yuv = make_yuv_options(layout, pitch_y, pitch_c, nb_frames)
+        _check(lib().fuifgpu_batch_pack_yuv420(self._h, int(first_image), int(n_images), C.byref(yuv), dst_device_ptr, int(image_stride), stream))
+
+    def download_yuv420(self, image, layout="i420", pitch_y=0, pitch_c=0, nb_frames=1):
+        """the raw YUV 4:2:0 frame(s) of one image of a keep = 2 batch as bytes -- for tight I420 the .yuv file `fuif -d x.fuif out.yuv`
+        writes (fuifgpu_batch_download_yuv420; padding bytes of pitched rows are 0); call after undo_transforms()"""
+        yuv = make_yuv_options(layout, pitch_y, pitch_c, nb_frames)
+        n = int(lib().fuifgpu_plan_yuv420_bytes(self.plan._h, C.byref(yuv)))
+        buf = np.zeros(max(n, 1), np.uint8)
+        _check(lib().fuifgpu_batch_download_yuv420(self._h, int(image), C.byref(yuv), buf.ctypes.data, None))
+        return buf[:n].tobytes()
+
     def out_planes(self, image):
+        """the output channels of one image as (h, w) int32 arrays, each with its own shape (a keep plan's channels differ in size)"""
         slab = np.zeros(max(self.plan.info.out_elems, 1), np.int32)
         _check(lib().fuifgpu_batch_download_out(self._h, image, slab.ctypes.data, None))
         return [slab[c["offset"]: c["offset"] + c["w"] * c["h"]].reshape(c["h"], c["w"]).copy() for c in self.plan.output_channels]
@@ -834,6 +874,42 @@ def unpack_yuv420(frame_device_ptr, w, h, y_device_ptr, cb_device_ptr, cr_device
     yuv = make_yuv_options(layout, pitch_y, pitch_c)
     _check(lib().fuifgpu_unpack_yuv420(frame_device_ptr, int(w), int(h), int(bit_depth), C.byref(yuv), y_device_ptr, cb_device_ptr, cr_device_ptr,
                                       flag_device_ptr, stream))
+
+
+def pack_yuv420(y_device_ptr, cb_device_ptr, cr_device_ptr, w, h, frame_device_ptr, bit_depth=8, layout="i420", pitch_y=0, pitch_c=0, stream=None):
+    """fuifgpu_pack_yuv420, the inverse of unpack_yuv420: three tight int32 planes in DEVICE memory (w*h, and twice ((w+1)/2) * ((h+1)/2)
+    samples) -> one raw 4:2:0 frame in device memory, every sample clamped to [0, 2^bit_depth - 1]; asynchronous on `stream`"""
+    yuv = make_yuv_options(layout, pitch_y, pitch_c)
+    _check(lib().fuifgpu_pack_yuv420(y_device_ptr, cb_device_ptr, cr_device_ptr, int(w), int(h), int(bit_depth), C.byref(yuv), frame_device_ptr, stream))
+
+
+def decode_yuv420(blobs, layout="i420", pitch_y=0, pitch_c=0, nb_frames=1, preview=-1):
+    """same-geometry `fuif -y` streams -> list of raw YUV 4:2:0 frames (bytes), the counterpart of encode_yuv420_batch: one batch whose
+    inverse schedule keeps the recorded [YCbCr, ChromaSubsample] pair (keep = 2), one pack launch, one copy to the host.  An image whose
+    status says corrupt or unsupported raises"""
+    plan = Plan(blobs[0], keep=2)
+    size = plan.yuv420_bytes(layout, pitch_y, pitch_c, nb_frames)
+    batch = Batch(plan, len(blobs), sum(len(b) for b in blobs))
+    L = lib()
+    dev = None
+    try:
+        batch.upload(blobs, preview)
+        batch.decode()
+        batch.undo_transforms()
+        dev = L.fuifgpu_dev_alloc(max(size * len(blobs), 16))
+        if not dev:
+            raise FuifGpuError(7, "decode_yuv420: no device memory for the frames")
+        batch.pack_yuv420(0, len(blobs), dev, layout, pitch_y, pitch_c, nb_frames)   # (refuses a plan that is no 4:2:0 picture)
+        st, _ = batch.status()
+        if (st & ~1).any():                  # (bit 0, truncated, is what a preview asks for)
+            raise FuifGpuError(2, "decode_yuv420: image status %s" % [int(v) for v in st])
+        host = np.zeros(max(size * len(blobs), 1), np.uint8)
+        _check(L.fuifgpu_dev_download(host.ctypes.data, dev, size * len(blobs)))
+        return [host[k * size: (k + 1) * size].tobytes() for k in range(len(blobs))]
+    finally:
+        if dev:
+            L.fuifgpu_dev_free(dev)
+        batch.close()
 
 
 def quantization_constant_yuv(quality, chroma_quality=None, squeeze=True, chroma_table=False, shift=0):

@@ -345,10 +345,16 @@ int fuifgpu_abi_version(void) { return FUIFGPU_ABI_VERSION; }
 
 void fuifgpu_build_chance_table(uint16_t *table8192, uint32_t alpha, int cut) { build_chance_table(table8192, alpha, cut); }
 
-int fuifgpu_plan_create(const uint8_t *blob, size_t size, fuifgpu_plan **out) {
+int fuifgpu_plan_create(const uint8_t *blob, size_t size, fuifgpu_plan **out) { return fuifgpu_plan_create_keep(blob, size, 0, out); }
+int fuifgpu_plan_keep(const fuifgpu_plan *plan, int *keep) {
+    if (!plan || !keep) return FUIFGPU_E_ARG;
+    *keep = plan->plan.keep;
+    return FUIFGPU_OK;
+}
+int fuifgpu_plan_create_keep(const uint8_t *blob, size_t size, int keep, fuifgpu_plan **out) {
     if (!blob || !out) return FUIFGPU_E_ARG;
     fuifgpu_plan *p = new fuifgpu_plan();
-    int r = parse_and_plan(blob, size, p->plan);
+    int r = parse_and_plan(blob, size, p->plan, keep);
     if (r != FUIFGPU_OK) {
         g_last_error = p->plan.message;
         delete p;
@@ -560,7 +566,7 @@ static int stage_streams(fuifgpu_batch *b, const uint8_t *const *blobs, const si
         if (off + padded + 256 > b->blob_cap) { g_last_error = "blob capacity exceeded"; return FUIFGPU_E_NOMEM; }  // the last 256-byte read window stays inside the allocation
         StreamJob &j = b->jobs[i];
         if (src < 0) {
-            int r = parse_and_plan(blobs[i], sizes[i], tmp);
+            int r = parse_and_plan(blobs[i], sizes[i], tmp, b->plan.keep);   // (the batch's own keep: the signatures of two schedule lengths differ)
             if (r != FUIFGPU_OK) { g_last_error = tmp.message; return r; }
             if (tmp.signature != b->plan.signature) { g_last_error = "image " + std::to_string(i) + " has a different geometry/transform chain"; return FUIFGPU_E_MISMATCH; }
             std::vector<GroupEntry> idx;
@@ -971,6 +977,86 @@ int fuifgpu_batch_download_packed(fuifgpu_batch *b, int image, int components, u
     hipFree(staging);
     if (rc != FUIFGPU_OK) return rc;
     if (e != hipSuccess) return hip_fail(e, "download_packed");
+    return FUIFGPU_OK;
+}
+
+// ---- raw 4:2:0 frames out (export/write_yuv.h:29-58 behind Image::undo_transforms(2), fuif.cpp:229-231) ------
+// Whether the plan's output channels are what write_YUV_file accepts (write_yuv.h:32-33, tightened to 4:2:0), the frame geometry the options
+// ask for, and where the three planes lie in one image's output slice: job.plane[] = slice + the plane's offset (slice may be NULL: sizes only)
+static int yuv420_layout(const Plan &p, const fuifgpu_yuv_options *yuv, const int32_t *slice, YuvGeom &g, YuvPackJob &job) {
+    if (p.keep != 2) return fail_msg(FUIFGPU_E_ARG, "yuv420 frames need a plan made with keep = 2 (fuifgpu_plan_create_keep)");
+    if (p.transforms.size() < 2 || p.transforms[0].id != TR_YCBCR || p.transforms[1].id != TR_SUBSAMPLE || p.outputs.size() != 3 ||
+        p.outputs[1].hshift != 1 || p.outputs[1].vshift != 1 || p.outputs[2].hshift != 1 || p.outputs[2].vshift != 1 || p.bit_depth > 14)
+        return fail_msg(FUIFGPU_E_UNSUPPORTED, "not a YCbCr 4:2:0 picture of at most 14 bits: no yuv420 frames");
+    int nbf = 1;
+    if (yuv && yuv->struct_size >= offsetof(fuifgpu_yuv_options, nb_frames) + sizeof(int32_t)) nbf = yuv->nb_frames;
+    if (nbf != 1 && (nbf != p.nb_frames || p.h % nbf)) return fail_msg(FUIFGPU_E_ARG, "yuv420: nb_frames is 1 (the strip) or the stream's frame count");
+    OKCHK(yuv_geometry(yuv, p.w, p.h / nbf, std::max(p.bit_depth, 8), nbf == 1, g, nullptr));
+    g.maxval = p.maxval;
+    job = YuvPackJob{};
+    for (int c = 0; c < 3; c++) {
+        const PlaneRef &pl = p.outputs[c].plane;
+        if (pl.w < (c ? g.cw : g.w) || pl.h < (int64_t)(c ? g.ch : g.h) * g.nb_frames)
+            return fail_msg(FUIFGPU_E_UNSUPPORTED, "yuv420: a plane smaller than the nominal frame");
+        job.plane[c] = slice ? slice + pl.off : nullptr;
+        job.row_pitch[c] = pl.w;
+    }
+    job.image_stride = p.out_elems;
+    return FUIFGPU_OK;
+}
+size_t fuifgpu_plan_yuv420_bytes(const fuifgpu_plan *plan, const fuifgpu_yuv_options *yuv) {
+    if (!plan) return 0;
+    YuvGeom g; YuvPackJob job;
+    if (yuv420_layout(plan->plan, yuv, nullptr, g, job) != FUIFGPU_OK) return 0;
+    return (size_t)(g.frame_bytes * g.nb_frames);
+}
+int fuifgpu_batch_pack_yuv420(fuifgpu_batch *b, int first_image, int n_images, const fuifgpu_yuv_options *yuv, uint8_t *dst_device, int64_t image_stride_bytes,
+                              void *stream) {
+    ON_BATCH_DEVICE(b);
+    if (!b || b->orphan || !dst_device || first_image < 0 || n_images < 1 || first_image + n_images > b->n_loaded || b->no_out) return FUIFGPU_E_ARG;
+    const Plan &p = b->plan;
+    YuvGeom g; YuvPackJob job;
+    OKCHK(yuv420_layout(p, yuv, b->d_out + (int64_t)first_image * p.out_elems, g, job));
+    const int64_t bytes = g.frame_bytes * g.nb_frames;
+    if (image_stride_bytes == 0) image_stride_bytes = bytes;
+    if (image_stride_bytes < bytes) return fail_msg(FUIFGPU_E_ARG, "yuv420: an image stride smaller than the frame(s) of one image");
+    job.dst = dst_device; job.dst_stride = image_stride_bytes;
+    launch_pack_yuv420(job, n_images, g, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return FUIFGPU_OK;
+}
+int fuifgpu_batch_download_yuv420(fuifgpu_batch *b, int image, const fuifgpu_yuv_options *yuv, uint8_t *host, void *stream) {
+    ON_BATCH_DEVICE(b);
+    if (!b || !host || image < 0 || image >= b->n_loaded) return FUIFGPU_E_ARG;
+    YuvGeom g; YuvPackJob job;
+    OKCHK(yuv420_layout(b->plan, yuv, nullptr, g, job));
+    const size_t bytes = (size_t)(g.frame_bytes * g.nb_frames);
+    uint8_t *staging = nullptr;
+    HIPCHK(hipMalloc((void **)&staging, bytes ? bytes : 1));
+    hipError_t e = hipMemsetAsync(staging, 0, bytes, (hipStream_t)stream);   // (pitch padding: the kernel writes samples only)
+    int rc = e == hipSuccess ? fuifgpu_batch_pack_yuv420(b, image, 1, yuv, staging, 0, stream) : FUIFGPU_OK;
+    if (e == hipSuccess && rc == FUIFGPU_OK) {
+        e = hipMemcpyAsync(host, staging, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream);
+        if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    }
+    hipFree(staging);
+    if (rc != FUIFGPU_OK) return rc;
+    if (e != hipSuccess) return hip_fail(e, "download_yuv420");
+    return FUIFGPU_OK;
+}
+int fuifgpu_pack_yuv420(const int32_t *y, const int32_t *cb, const int32_t *cr, int w, int h, int bit_depth, const fuifgpu_yuv_options *yuv, void *frame_device,
+                        void *stream) {
+    if (w < 0 || h < 0) return FUIFGPU_E_ARG;
+    if ((int64_t)w * h == 0) return FUIFGPU_OK;
+    YuvGeom g;
+    OKCHK(yuv_geometry(yuv, w, h, bit_depth, true, g, nullptr));
+    if (!frame_device || !y || !cb || !cr) return FUIFGPU_E_ARG;
+    YuvPackJob job{};
+    job.plane[0] = y; job.plane[1] = cb; job.plane[2] = cr;
+    job.row_pitch[0] = g.w; job.row_pitch[1] = job.row_pitch[2] = g.cw;
+    job.dst = static_cast<uint8_t *>(frame_device);
+    launch_pack_yuv420(job, 1, g, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
     return FUIFGPU_OK;
 }
 

@@ -149,6 +149,7 @@ struct Plan {
     std::vector<ChannelGeom> coded;             // channel table the entropy stage fills
     int64_t coef_elems = 0;                     // per-image coefficient slab (int32 elements)
     // inverse schedule (image/image.cpp:94-115)
+    int keep = 0;                               // transforms left standing: the schedule undoes transforms[size-1 .. keep] and, unless keep == 0, makes no final clamp
     std::vector<Op> ops;
     std::vector<PlaneRef> idct_src;
     std::vector<int64_t> widen;                 // {element offset, elements} pairs: the coded planes some inverse kernel reads (or rewrites) as int32 --
@@ -198,6 +199,17 @@ struct YuvGeom {
     int64_t frame_bytes;           // from one frame to the next
     int64_t row_bytes(bool chroma) const { return chroma ? (int64_t)cw * bytes * (nv12 ? 2 : 1) : (int64_t)w * bytes; }
 };
+// The decoder's packing of Y, Cb, Cr planes into raw 4:2:0 frames (transforms.hip k_pack_yuv420; export/write_yuv.h:29-58), the inverse of the
+// unpacking: picture k of a launch reads plane[p] + k * image_stride (int32 samples, rows row_pitch[p] samples apart -- a plane may be wider
+// and taller than the frame, iDCT block padding, and is cropped) and writes YuvGeom::nb_frames frames back to back at dst + k * dst_stride;
+// frame f's rows are rows f * (the frame's rows) .. of the planes
+struct YuvPackJob {
+    const int32_t *plane[3];
+    int64_t image_stride;          // samples from one picture's planes to the next one's
+    int32_t row_pitch[3];
+    uint8_t *dst;
+    int64_t dst_stride;            // bytes from one picture's frames to the next one's
+};
 // every frame of every job in one launch (capi.hip): jobs_host[k].src / out are device pointers; *flag_host = 1 if a sample exceeded
 // g.maxval.  Synchronous (null stream)
 int unpack_yuv420_gpu(const YuvJob *jobs_host, int n_jobs, const YuvGeom &g, int *flag_host);
@@ -223,7 +235,8 @@ void build_index_trailer(const std::vector<GroupEntry> &groups, std::vector<uint
 bool parse_index_trailer(const uint8_t *blob, size_t n, size_t data_start, int nch, std::vector<GroupEntry> &groups, size_t *stream_end);
 
 // host planner (plan.cpp)
-int parse_and_plan(const uint8_t *blob, size_t n, Plan &plan);
+// keep: Image::undo_transforms(keep) -- 0 <= keep <= the number of transforms, else FUIFGPU_E_ARG
+int parse_and_plan(const uint8_t *blob, size_t n, Plan &plan, int keep = 0);
 void build_chance_table(uint16_t *table8192, uint32_t alpha, int cut);
 
 }  // namespace fuifgpu

@@ -900,7 +900,8 @@ struct Builder {
         }
     }
 
-    bool finalize() {
+    // keep: transforms left standing (Image::undo_transforms(keep), image/image.cpp:94-115); the final clamp is only made for keep == 0 (:107)
+    bool finalize(int keep) {
         // every plane still referenced by a live channel is a final plane
         int nops_before = (int)ops.size();
         std::vector<int> last_writer(planes.size(), -1), last_kind(planes.size(), 0);
@@ -958,6 +959,7 @@ struct Builder {
         // writer, skip when the last writer already clamps to [minval,maxval], else clamp in place
         std::vector<int> clamp_fused(ops.size(), 0);
         for (auto &ch : live) {
+            if (keep != 0) break;   // (a copy op without clamp_out is a plain widening copy: transforms.hip launch_op)
             if ((int64_t)ch.w * ch.h == 0) continue;
             int pl = ch.plane;
             int lw = last_writer[pl], lk = last_kind[pl];
@@ -1059,8 +1061,9 @@ void build_chance_table(uint16_t *t, uint32_t factor, int cut) {
     for (unsigned i = 1; i < size; i++) t[i * 2] = (uint16_t)(size - t[(size - i) * 2 + 1]);
 }
 
-int parse_and_plan(const uint8_t *blob, size_t n, Plan &plan) {
+int parse_and_plan(const uint8_t *blob, size_t n, Plan &plan, int keep) {
     plan = Plan();
+    plan.keep = keep;
     ByteReader io{blob, n, 0, false};
     if (n < 4 || (memcmp(blob, "FUIF", 4) && memcmp(blob, "FUAF", 4))) {
         plan.error = FUIFGPU_E_NOT_FUIF;
@@ -1133,6 +1136,11 @@ int parse_and_plan(const uint8_t *blob, size_t n, Plan &plan) {
     }
     if (io.eof) { plan.error = FUIFGPU_E_CORRUPT; plan.message = "truncated header"; return plan.error; }
     plan.data_start = io.pos;
+    if (keep < 0 || keep > (int)plan.transforms.size()) {
+        plan.error = FUIFGPU_E_ARG;
+        plan.message = "keep is 0 .. the number of transforms (" + std::to_string(plan.transforms.size()) + ")";
+        return plan.error;
+    }
 
     // A parameter-less Permute at the END of the list: right after its meta-channel the reference puts the metadata of the
     // channels still to be decoded in coded order (encoding.cpp:576-596,712).  Their geometry is identical (meta_permute
@@ -1159,8 +1167,8 @@ int parse_and_plan(const uint8_t *blob, size_t n, Plan &plan) {
     }
     plan.coef_elems = off;
 
-    // inverse schedule: Image::undo_transforms pops the list from the back (image/image.cpp:95-106)
-    for (int i = (int)plan.transforms.size() - 1; i >= 0; i--) {
+    // inverse schedule: Image::undo_transforms(keep) pops the list from the back until `keep` transforms are left (image/image.cpp:95-106)
+    for (int i = (int)plan.transforms.size() - 1; i >= keep; i--) {
         TransformDesc &t = plan.transforms[i];
         bool ok = true;
         switch (t.id) {
@@ -1182,7 +1190,7 @@ int parse_and_plan(const uint8_t *blob, size_t n, Plan &plan) {
         }
         if (!ok) return plan.error ? plan.error : (plan.error = FUIFGPU_E_CORRUPT);
     }
-    if (!b.finalize()) return plan.error;
+    if (!b.finalize(keep)) return plan.error;
 
     uint64_t hsh = 1469598103934665603ull;
     int hdr[8] = {plan.w, plan.h, plan.bit_depth, plan.nb_channels, plan.max_properties, plan.nb_frames, (int)plan.transforms.size(), 0};
@@ -1191,6 +1199,7 @@ int parse_and_plan(const uint8_t *blob, size_t n, Plan &plan) {
         hsh = fnv1a(hsh, &t.id, sizeof(int));
         if (!t.params.empty()) hsh = fnv1a(hsh, t.params.data(), t.params.size() * sizeof(int));
     }
+    if (keep != 0) hsh = fnv1a(hsh, &keep, sizeof(int));   // (a shortened schedule: other ops, other output channels; keep == 0 hashes as it always did)
     plan.signature = hsh;
     return FUIFGPU_OK;
 }

@@ -51,6 +51,9 @@ void launch_channel_stats(const StatsRec *dev_table, int n_recs, StatsRec one, i
 // raw YUV 4:2:0 frames -> tight int32 planes (import/read_yuv.h:29-63): every frame of every job of a device table in one launch, or
 // dev_table == NULL: the one job `one`.  dev_flag (may be NULL): a word that gets a bit set if a sample exceeds g.maxval
 void launch_unpack_yuv420(const YuvJob *dev_table, int n_jobs, YuvJob one, const YuvGeom &g, int32_t *dev_flag, hipStream_t stream);
+// int32 Y, Cb, Cr planes -> raw YUV 4:2:0 frames, clamped to [0, g.maxval] (export/write_yuv.h:29-58): the g.nb_frames frames of each of
+// n_pictures pictures in one launch; picture k's planes and frames lie k * job.image_stride samples / k * job.dst_stride bytes behind picture 0's
+void launch_pack_yuv420(const YuvPackJob &job, int n_pictures, const YuvGeom &g, hipStream_t stream);
 // forward Palette (transform/palette.h:92-142).  Several channels: the distinct tuples of nb planes into an open-addressing table of
 // `capacity` (a power of two > 2 * limit) zero-initialised 64-bit keys; dev_ctl: four zero-initialised words {distinct colours, too many,
 // the all-zero key occurs, a sample outside int16}.  Then every sample's colour number from the table and the ranks of its slots.

@@ -1190,6 +1190,102 @@ void launch_unpack_yuv420(const YuvJob *dev_table, int n_jobs, YuvJob one, const
                            dev_table ? dev_table + z0 / g.nb_frames : nullptr, one, g, segs, dev_flag);
     }
 }
+// export/write_yuv.h:29-58 on the GPU, the inverse of k_unpack_yuv420: tight (or block-padded, then cropped) int32 planes -> raw 4:2:0 frames,
+// every sample CLAMP(v, 0, maxval) (write_yuv.h:49), one byte each or two little-endian; planar, or the chroma samples as one plane of Cb, Cr
+// pairs; rows `pitch` bytes apart.  Bandwidth bound, 6 bytes in and 1.5-3 out per pixel; no LDS.  The same grid and lane mapping as the
+// unpacking: a wavefront takes one row segment, a lane reads 4 samples (one int32x4 load wherever the source is on a 16-byte boundary, else
+// four dword loads, still consecutive across the lanes) -- in a plane of pairs 4 + 4 -- and writes ONE aligned word of 4 or 8 (pairs: 8 or 16)
+// bytes; consecutive lanes write consecutive words.  The ELEMENTS in front of the row's first aligned destination word and behind its last
+// whole one, at most 3 (7) each, go one by one as byte stores in the first lanes of the row's first segment; a row of 16-bit samples on an odd
+// byte goes that way as a whole.  No store touches a byte outside [row, row + row bytes): pitch padding and whatever follows the last sample
+// of the last row stay the caller's.
+typedef uint32_t yuv_word2_t __attribute__((vector_size(8)));
+typedef uint32_t yuv_word4_t __attribute__((vector_size(16)));
+__device__ __forceinline__ void load_quad(const int32_t *src, int32_t *v) {
+    if ((reinterpret_cast<uintptr_t>(src) & 15) == 0) { const yuv_quad_t q = *reinterpret_cast<const yuv_quad_t *>(src); v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3]; }
+    else { v[0] = src[0]; v[1] = src[1]; v[2] = src[2]; v[3] = src[3]; }
+}
+template <int BYTES>
+__device__ __forceinline__ void yuv_store_element(uint8_t *p, uint32_t v) {   // one by one: byte stores, any address
+    p[0] = (uint8_t)v;
+    if (BYTES == 2) p[1] = (uint8_t)(v >> 8);
+}
+// one row segment: `n` elements to `row`; PAIRS: element e is component e & 1 of pair e >> 1 and comes from in0 / in1 [e >> 1]; else from in0[e].
+// k: the lane's word among the row's; first_segment: this wavefront also takes the row's ends
+template <int BYTES, bool PAIRS>
+__device__ __forceinline__ void pack_row_segment(uint8_t *row, int64_t n, const int32_t *in0, const int32_t *in1, int64_t k, bool first_segment, int lane,
+                                                 int maxval) {
+    constexpr int E = PAIRS ? 8 : 4, VB = E * BYTES;            // elements and bytes of one word store
+    const int64_t to_aligned = (int64_t)((VB - (reinterpret_cast<uintptr_t>(row) & (VB - 1))) & (VB - 1)) / BYTES;
+    const bool split_samples = BYTES == 2 && (reinterpret_cast<uintptr_t>(row) & 1);   // 16-bit samples on odd addresses: no aligned word holds whole ones, the row is all head
+    const int64_t head = to_aligned < n && !split_samples ? to_aligned : n, nvec = (n - head) / E, tail = n - head - nvec * E;
+    if (k < nvec) {
+        const int64_t e0 = head + k * E;
+        int32_t s[E];
+        if constexpr (!PAIRS) load_quad(in0 + e0, s);
+        else {
+            // even e0: elements 0, 2, 4, 6 are Cb of pairs e0/2 .. e0/2 + 3 and the odd ones their Cr; odd e0: the odd elements are Cb of pairs
+            // (e0+1)/2 .., the even ones Cr of the pairs one before
+            const bool swapped = (e0 & 1) != 0;
+            int32_t a[4], b[4];
+            load_quad((swapped ? in1 : in0) + (e0 >> 1), a);
+            load_quad((swapped ? in0 : in1) + ((e0 + 1) >> 1), b);
+            for (int i = 0; i < 4; i++) { s[2 * i] = a[i]; s[2 * i + 1] = b[i]; }
+        }
+        uint32_t words[VB / 4];
+        for (int i = 0; i < VB / 4; i++) words[i] = 0;
+        for (int i = 0; i < E; i++) {
+            const uint32_t v = (uint32_t)clampi(s[i], 0, maxval);
+            if (BYTES == 1) words[i >> 2] |= v << (8 * (i & 3));
+            else words[i >> 1] |= v << (16 * (i & 1));
+        }
+        uint8_t *dst = row + e0 * BYTES;
+        if constexpr (VB == 4) *reinterpret_cast<uint32_t *>(dst) = words[0];
+        else if constexpr (VB == 8) { const yuv_word2_t v = {words[0], words[1]}; *reinterpret_cast<yuv_word2_t *>(dst) = v; }
+        else { const yuv_word4_t v = {words[0], words[1], words[2], words[3]}; *reinterpret_cast<yuv_word4_t *>(dst) = v; }
+    }
+    if (first_segment)   // the ends: at most E - 1 elements each (a row of split samples: all of it), one per lane and pass
+        for (int64_t i = lane; i < head + tail; i += 64) {
+            const int64_t e = i < head ? i : i + nvec * E;
+            const int32_t v = !PAIRS ? in0[e] : ((e & 1) ? in1 : in0)[e >> 1];
+            yuv_store_element<BYTES>(row + e * BYTES, (uint32_t)clampi(v, 0, maxval));
+        }
+}
+__global__ __launch_bounds__(256) void k_pack_yuv420(YuvPackJob job, YuvGeom g, int segs) {
+    const int pic = blockIdx.z / g.nb_frames, f = blockIdx.z - pic * g.nb_frames;
+    const int p = blockIdx.y;                       // 0: Y; planar: 1 Cb, 2 Cr; nv12: 1 the plane of pairs
+    const int pw = p ? g.cw : g.w, ph = p ? g.ch : g.h;
+    const int rows4 = blockIdx.x / segs, seg = blockIdx.x - rows4 * segs;
+    const int y = rows4 * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // a block: four rows, one wavefront each
+    if (y >= ph) return;
+    const bool pairs = p && g.nv12;
+    const int64_t plane_at = p == 0 ? 0 : g.pitch_y * g.h + (p == 2 ? g.pitch_c * g.ch : 0);
+    uint8_t *row = job.dst + pic * job.dst_stride + f * g.frame_bytes + plane_at + y * (p ? g.pitch_c : g.pitch_y);
+    const int64_t src_row = (int64_t)f * ph + y;    // the frames of a clip are stacked in every plane
+    const int32_t *in0 = job.plane[p] + pic * job.image_stride + src_row * job.row_pitch[p];
+    const int32_t *in1 = pairs ? job.plane[2] + pic * job.image_stride + src_row * job.row_pitch[2] : nullptr;
+    const int64_t k = (int64_t)seg * 64 + lane;
+    if (g.bytes == 1) {
+        if (pairs) pack_row_segment<1, true>(row, 2 * (int64_t)pw, in0, in1, k, seg == 0, lane, g.maxval);
+        else pack_row_segment<1, false>(row, pw, in0, in1, k, seg == 0, lane, g.maxval);
+    } else {
+        if (pairs) pack_row_segment<2, true>(row, 2 * (int64_t)pw, in0, in1, k, seg == 0, lane, g.maxval);
+        else pack_row_segment<2, false>(row, pw, in0, in1, k, seg == 0, lane, g.maxval);
+    }
+}
+void launch_pack_yuv420(const YuvPackJob &job, int n_pictures, const YuvGeom &g, hipStream_t stream) {
+    if (n_pictures <= 0 || g.w <= 0 || g.h <= 0 || g.nb_frames <= 0 || g.nb_frames > 65535) return;   // (the callers refuse longer clips)
+    // a luma row has at most w / 4 whole words, a chroma row or a row of pairs no more; every row has a first segment for its ends
+    const int segs = std::max(1, (g.w / 4 + 63) / 64);
+    const int64_t frames = (int64_t)n_pictures * g.nb_frames, per_launch = 65535 / g.nb_frames * g.nb_frames;   // (grid.z holds 65535: whole pictures per launch)
+    for (int64_t z0 = 0; z0 < frames; z0 += per_launch) {
+        const int64_t nz = std::min<int64_t>(frames - z0, per_launch), pic0 = z0 / g.nb_frames;
+        YuvPackJob part = job;
+        for (int p = 0; p < 3; p++) part.plane[p] += pic0 * job.image_stride;
+        part.dst += pic0 * job.dst_stride;
+        hipLaunchKernelGGL(k_pack_yuv420, dim3((unsigned)(segs * ((g.h + 3) / 4)), g.nv12 ? 2u : 3u, (unsigned)nz), dim3(256), 0, stream, part, g, segs);
+    }
+}
 // ---------------------------------------------------------------------------------------------
 // Forward Palette (transform/palette.h:92-142): which colour tuples occur, then every pixel's colour number.  The reference inserts every
 // pixel into a std::set and searches the palette linearly per pixel; here the set is built by all lanes at once and the order of the
@@ -1557,10 +1653,13 @@ void launch_op(const Op &op, const Bases &b, const PlaneRef *dev_list, ChannelMe
                                    op.p0, op.p1, op.clamp_out, op.lo, op.hi);
             break;
         case OP_COPY_CLAMP:
-        case OP_CLAMP:
+        case OP_CLAMP: {
+            // a copy without the fused final clamp (a coded plane that is a final plane of a kept-transform schedule, image.cpp:107): the whole int32 range passes
+            const bool plain = op.kind == OP_COPY_CLAMP && !op.clamp_out;
             hipLaunchKernelGGL(k_clamp, grid1d((int64_t)op.dst[0].w * op.dst[0].h, 256, n_images), dim3(256), 0, stream, b, op.src[0], op.dst[0],
-                               op.lo, op.hi);
+                               plain ? INT32_MIN : op.lo, plain ? INT32_MAX : op.hi);
             break;
+        }
         case OP_PALETTE:
             if ((int64_t)op.dst[0].w * op.dst[0].h <= 0) break;
             hipLaunchKernelGGL(k_inv_palette, grid1d((int64_t)op.dst[0].w * op.dst[0].h, 256, n_images), dim3(256), 0, stream, b, op.src[0],

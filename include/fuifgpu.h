@@ -68,6 +68,16 @@ int fuifgpu_abi_version(void);
 
 /* ---- host side: header parse + planning (no GPU needed) ------------------------------------ */
 int fuifgpu_plan_create(const uint8_t *blob, size_t size, fuifgpu_plan **out);
+/* A plan whose inverse schedule stops with `keep` transforms left standing: Image::undo_transforms(keep) (image/image.cpp:94-115),
+ * what `fuif -d x.fuif out.yuv` runs with keep = 2 (fuif.cpp:229-231).  0 <= keep <= nb_transforms, else FUIFGPU_E_ARG; keep = 0 is
+ * fuifgpu_plan_create.  With keep != 0 there is no final clamp (image.cpp:107), the output channels are the channel list the reference
+ * has at that point -- remaining meta-channels first, zero-size channels included, every channel with its own size and shifts -- and
+ * nb_ops, out_elems, tmp_elems, nb_output_channels describe the shortened schedule; the signature differs from the keep = 0 plan's.  A batch
+ * made from such a plan (a sibling: its primary's) plans every uploaded stream with the same keep; fuifgpu_batch_undo_transforms,
+ * _undo_transforms_to, _download_out, _out_ptr and fuifgpu_plane_checksums work on it unchanged, fuifgpu_batch_pack_out keeps its rule
+ * (a channel smaller than w x h is FUIFGPU_E_ARG).  Both entry points are found by symbol lookup: the ABI version does not change. */
+int fuifgpu_plan_create_keep(const uint8_t *blob, size_t size, int keep, fuifgpu_plan **out);
+int fuifgpu_plan_keep(const fuifgpu_plan *plan, int *keep);
 void fuifgpu_plan_destroy(fuifgpu_plan *plan);
 int fuifgpu_plan_info(const fuifgpu_plan *plan, fuifgpu_image_info *info);
 int fuifgpu_plan_coded_channel(const fuifgpu_plan *plan, int index, fuifgpu_channel_desc *desc);
@@ -93,7 +103,8 @@ void fuifgpu_batch_destroy(fuifgpu_batch *batch);
  * slice before the next.  fuifgpu_batch_undo_transforms, _out_ptr, _download_out and _pack_out are refused on such a batch.
  * The reference has no counterpart: it decodes one image at a time (fuif.cpp:213-233). */
 int fuifgpu_batch_create_streaming(const fuifgpu_plan *plan, int n_images, size_t blob_capacity_bytes, int tmp_images, fuifgpu_batch **out);
-/* Image::undo_transforms(0) for images [first_image, first_image + n_images) of the current decode; their output planes go to
+/* Image::undo_transforms(0) -- undo_transforms(keep) for a plan made with fuifgpu_plan_create_keep, with its smaller out_elems -- for
+ * images [first_image, first_image + n_images) of the current decode; their output planes go to
  * out_device (n_images * out_elems int32, device memory; plan output-channel offsets apply inside each image's slice).  Any
  * batch takes it; every image once per decode (a range that repeats an image, or a mix with fuifgpu_batch_undo_transforms, is
  * FUIFGPU_E_ARG).  A range counts as done once the call has queued it; after a failed call (a HIP error) decode again before
@@ -128,7 +139,8 @@ int fuifgpu_batch_decode(fuifgpu_batch *batch, void *stream);
 
 /* replaces Image::undo_transforms(0) (image/image.cpp:94-115) for every image of the batch:
  * inverse Squeeze / Quantize / DCT / ChromaSubsample / YCoCg / YCbCr + final clamp into the
- * output slab. */
+ * output slab.  A plan made with fuifgpu_plan_create_keep: undo_transforms(keep), which stops with `keep`
+ * transforms left and makes no final clamp. */
 int fuifgpu_batch_undo_transforms(fuifgpu_batch *batch, void *stream);
 /* (once per decode: the inverse of Approximate rewrites the per-channel metadata, so a second call is refused with FUIFGPU_E_ARG
  * until the batch is decoded again.  The coefficient slab itself is not touched -- the kernels work on a widened copy of a chunk
@@ -482,6 +494,34 @@ int fuifgpu_encode_yuv420(const void *const *frames, int on_device, int n, int w
  * value if any sample exceeds 2^bit_depth - 1, and is not written otherwise.  w * h == 0 touches nothing. */
 int fuifgpu_unpack_yuv420(const void *frame_device, int w, int h, int bit_depth, const fuifgpu_yuv_options *yuv, int32_t *y_out, int32_t *cb_out,
                           int32_t *cr_out, int32_t *flag_device, void *stream);
+/* ---- YUV 4:2:0 frames OUT: what `fuif -d x.fuif out.yuv` writes (fuif.cpp:229-231: undo_transforms(2), then export/write_yuv.h:29-58) ----
+ * The plan is made with fuifgpu_plan_create_keep(.., 2, ..): the recorded [YCbCr, ChromaSubsample] pair stays, the decoded Y, Cb, Cr
+ * planes are neither upsampled nor colour-transformed, and a kernel (the inverse of fuifgpu_unpack_yuv420's) writes them as raw frame
+ * bytes in the layout fuifgpu_yuv_options describes -- every sample CLAMP(v, 0, maxval) (write_yuv.h:49), one byte for maxval < 256, else
+ * two little-endian.  Eligible (write_yuv.h:32-33, tightened to 4:2:0): keep == 2, transforms 0 and 1 are YCbCr and ChromaSubsample, exactly
+ * three output channels, channels 1 and 2 with hshift == vshift == 1, at most 14 bits.  A plan with another keep is FUIFGPU_E_ARG, a
+ * keep = 2 plan of another shape (4:2:2, RGB, a palette ..) FUIFGPU_E_UNSUPPORTED.  The frame is w x h luma and (w+1)/2 x (h+1)/2 chroma
+ * samples of the plan's w, h; a plane that is larger (iDCT block padding of JPEG-shaped streams) is cropped, a smaller one is
+ * FUIFGPU_E_UNSUPPORTED.  yuv->nb_frames is 1 -- the stacked strip as write_YUV_file writes it: all of Y, all of Cb, all of Cr -- or the
+ * stream's nb_frames: the frames back to back as fuifgpu_encode_yuv420 reads them (an odd frame height is then FUIFGPU_E_ARG, as there);
+ * anything else is FUIFGPU_E_ARG.  yuv->framerate is not looked at.  No byte outside a row's samples is written: pitch padding stays the
+ * caller's.  All found by symbol lookup: the ABI version does not change. */
+/* bytes of one image's frame(s) for these options, nb_frames * (pitch_y * fh + pitch_c * ((fh+1)/2) * (I420: 2, NV12: 1)); 0 = this plan
+ * cannot be written as 4:2:0 frames (or the options are refused) */
+size_t fuifgpu_plan_yuv420_bytes(const fuifgpu_plan *plan, const fuifgpu_yuv_options *yuv);
+/* replaces write_YUV_file's loops (write_yuv.h:46-53) for images [first_image, first_image + n_images) of the batch, after
+ * fuifgpu_batch_undo_transforms, in ONE launch: image k's frame(s) go to dst_device + k * image_stride_bytes (0 = tight; smaller than
+ * fuifgpu_plan_yuv420_bytes: FUIFGPU_E_ARG).  Asynchronous on stream.  Refused on a streaming batch (no output slab: fuifgpu_pack_yuv420
+ * on the slices fuifgpu_batch_undo_transforms_to wrote) */
+int fuifgpu_batch_pack_yuv420(fuifgpu_batch *batch, int first_image, int n_images, const fuifgpu_yuv_options *yuv, uint8_t *dst_device,
+                              int64_t image_stride_bytes, void *stream);
+/* one image into HOST memory, fuifgpu_plan_yuv420_bytes bytes (packs into a temporary device buffer whose padding bytes are 0, copies,
+ * synchronises the stream): the bytes of the .yuv file of fuif.cpp:229-231 for tight I420 */
+int fuifgpu_batch_download_yuv420(fuifgpu_batch *batch, int image, const fuifgpu_yuv_options *yuv, uint8_t *host, void *stream);
+/* the packing alone on raw device planes, no batch (write_yuv.h:46-53 for one frame; yuv->nb_frames is not looked at): the inverse of
+ * fuifgpu_unpack_yuv420 -- y w x h, cb and cr (w+1)/2 x (h+1)/2, tight int32, bit_depth 8..14.  Asynchronous on stream.  w * h == 0 touches nothing. */
+int fuifgpu_pack_yuv420(const int32_t *y, const int32_t *cb, const int32_t *cr, int w, int h, int bit_depth, const fuifgpu_yuv_options *yuv,
+                        void *frame_device, void *stream);
 /* fuifgpu_quantization_constant for `-y` input: the same tables behind the two factors of fuif.cpp:432-434 */
 int fuifgpu_quantization_constant_yuv(float quality, float chroma_quality, int squeeze_option, int chroma_table, int shift);
 /* host: the constant fuif.cpp:459-503 gives one channel -- squeeze_option = opt->squeeze (the OPTION, not whether the picture was large
