@@ -41,7 +41,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 def build(force=False, verbose=False):
     """Compile libfuifgpu.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(_HERE, "csrc", s) for s in _SOURCES]
-    deps = srcs + [os.path.join(_HERE, "csrc", h) for h in ("fuifgpu_internal.h", "maniac_decode.h", "maniac_encode.h", "transforms.h", "squeeze_arith.h")]
+    deps = srcs + [os.path.join(_HERE, "csrc", h) for h in ("fuifgpu_internal.h", "maniac_decode.h", "maniac_encode.h", "tree_learn.h", "transforms.h", "squeeze_arith.h")]
     deps.append(os.path.join(_HERE, "..", "include", "fuifgpu.h"))
     if os.environ.get("FUIF_AMD_LIB"):
         return _LIB_PATH
@@ -150,6 +150,12 @@ def make_lossy_options(quality=None, chroma_quality=None):
     return LossyOptions(C.sizeof(LossyOptions), 100.0 if quality is None else float(quality), 101.0 if chroma_quality is None else float(chroma_quality))
 
 
+class LearnOptions(C.Structure):
+    """fuifgpu_learn_options (include/fuifgpu.h): the tree learner's limits, for learn_tree"""
+    _fields_ = [("struct_size", C.c_uint32), ("max_nodes", C.c_int32), ("max_depth", C.c_int32), ("min_leaf", C.c_int32), ("split_bits", C.c_int32),
+                ("scale", C.c_double)]
+
+
 def make_encode_options(*fields):
     """EncodeOptions with struct_size set, the fields behind it in header order"""
     return EncodeOptions(C.sizeof(EncodeOptions), *fields)
@@ -173,6 +179,7 @@ ABI_SYMBOLS = [
     "fuifgpu_encode_animation", "fuifgpu_encode_animations", "fuifgpu_fwd_match_frames",
     "fuifgpu_encode_yuv420", "fuifgpu_unpack_yuv420", "fuifgpu_quantization_constant_yuv",
     "fuifgpu_plan_create_keep", "fuifgpu_plan_keep", "fuifgpu_plan_yuv420_bytes", "fuifgpu_batch_pack_yuv420", "fuifgpu_batch_download_yuv420", "fuifgpu_pack_yuv420",
+    "fuifgpu_learn_tree", "fuifgpu_encode_learn_traffic",
     "fuifgpu_plane_checksums", "fuifgpu_device_count", "fuifgpu_set_device", "fuifgpu_get_device", "fuifgpu_batch_device", "fuifgpu_peer_copy", "fuifgpu_batch_set_in_flight",
 ]
 
@@ -291,6 +298,8 @@ def lib():
     L.fuifgpu_batch_download_yuv420.argtypes = [vp, C.c_int, C.POINTER(YuvOptions), vp, vp]
     L.fuifgpu_pack_yuv420.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(YuvOptions), vp, vp]
     L.fuifgpu_encode_plane_traffic.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.fuifgpu_encode_learn_traffic.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.fuifgpu_learn_tree.argtypes = [vp, vp, C.c_int64, C.c_int, C.POINTER(LearnOptions), C.c_int, vp, C.c_int, C.POINTER(C.c_int)]
     L.fuifgpu_quantization_constant.argtypes = [C.c_float, C.c_float, C.c_int, C.c_int, C.c_int]
     L.fuifgpu_encode_image.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.fuifgpu_encode_images.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(EncodeOptions), C.POINTER(vp), C.POINTER(C.c_size_t)]
@@ -933,6 +942,42 @@ def encode_plane_traffic():
     a, b = C.c_uint64(0), C.c_uint64(0)
     _check(lib().fuifgpu_encode_plane_traffic(C.byref(a), C.byref(b)))
     return int(a.value), int(b.value)
+
+
+def encode_learn_traffic():
+    """(sample bytes, statistic bytes) the tree learner of the last encode call of this thread copied device->host
+    (fuifgpu_encode_learn_traffic): tree_mode 1 brings the samples of device-only channels, tree_mode 2 shortlists and record slices"""
+    a, b = C.c_uint64(0), C.c_uint64(0)
+    _check(lib().fuifgpu_encode_learn_traffic(C.byref(a), C.byref(b)))
+    return int(a.value), int(b.value)
+
+
+LEARN_WHERE = {"host": 0, "gpu": 1, "levelwise": 2}
+
+
+def learn_tree(props, bucket, n_samples=None, nprops=None, where="host", max_nodes=4095, max_depth=14, min_leaf=48, split_bits=0, scale=1.0, cap=None):
+    """The writer's tree learner on one sample set (fuifgpu_learn_tree) -> (n_nodes, 4) int32 array of {prop, split, gt, le}, prop -1 a leaf.
+    where: "host" (0, the recursive learner of tree_mode 1), "levelwise" (2, level by level with plain C++ statistics) -- props an
+    (n_samples, nprops) int32 array, bucket n_samples uint8 classes 0..16 -- or "gpu" (1, level by level with the kernels of tree_mode 2):
+    props and bucket are device addresses (ints) of the same two arrays, with n_samples and nprops given"""
+    code = LEARN_WHERE.get(where, -1) if isinstance(where, str) else int(where)
+    if code == 1:
+        p_ptr, b_ptr = int(props), int(bucket)
+        n, k = int(n_samples), int(nprops)
+    else:
+        p = np.ascontiguousarray(props, dtype=np.int32)
+        b = np.ascontiguousarray(bucket, dtype=np.uint8)
+        if p.ndim != 2 or b.ndim != 1 or b.shape[0] != p.shape[0]:
+            raise FuifGpuError(4, "learn_tree: props is (n_samples, nprops), bucket n_samples classes")
+        n, k = p.shape
+        p_ptr, b_ptr = p.ctypes.data, b.ctypes.data
+    if cap is None:
+        cap = max(1, min(int(max_nodes), 2 * max(n, 0) + 1)) if max_nodes >= 1 else 1
+    out = np.zeros((max(int(cap), 1), 4), np.int32)
+    count = C.c_int(0)
+    opt = LearnOptions(C.sizeof(LearnOptions), int(max_nodes), int(max_depth), int(min_leaf), int(split_bits), float(scale))
+    _check(lib().fuifgpu_learn_tree(p_ptr, b_ptr, n, k, C.byref(opt), code, out.ctypes.data, int(cap), C.byref(count)))
+    return out[: count.value].copy()
 
 
 def quantization_constant(quality, chroma_quality=None, squeeze=True, chroma_table=False, shift=0):

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "fuifgpu_internal.h"
+#include "tree_learn.h"
 
 namespace fuifgpu {
 
@@ -56,7 +57,7 @@ struct LearnJobDev {       // what k_learn_samples_jobs sees of one job; all poi
     EncGroup g;
     int64_t n_samples, stride;   // sample s is pixel s * stride (row-major)
     int32_t nprops, pad;         // 2 * g.nrefs + 13
-    int32_t *props;              // n_samples rows of nprops properties
+    int32_t *props;              // n_samples rows of nprops properties (k_learn_samples_cols_jobs: nprops columns of n_samples)
     uint8_t *bucket;             // n_samples residual classes: 0 for a zero residual d, else ilog2(|d|) + 1
 };
 struct LearnJob {          // host side of one job
@@ -73,6 +74,27 @@ struct LearnSamples {      // every job's rows and buckets, as they came back in
 };
 // Computes what the host learner's sampling loop computes (writer.cpp encode_group) for every job, in its order.
 int learn_samples_jobs_gpu(const std::vector<LearnJob> &jobs, LearnSamples &out);
+
+// ---- the level-wise tree learner's statistics on the GPU (tree_mode 2; csrc/tree_learn.h has the host side) ---------------------------------
+struct LearnTreeJobDev {   // what the learner kernels see of one learning group; all pointers are device pointers
+    const int32_t *cols;         // nprops columns of n_samples properties: column-major, so that a (node, property) scan reads one column
+    const uint8_t *bucket;       // n_samples residual classes
+    int32_t *idx0, *idx1;        // the samples of every node as a segment of sample numbers, ping-pong between the levels
+    int64_t n_samples;
+    int32_t nprops, pad;
+};
+struct LearnTreeJob {      // host side: what to sample (as LearnJob), how to learn, the learned tree
+    LearnJob sample;
+    LearnParams prm;
+    std::vector<LearnNode> nodes;
+};
+// Samples every job on the device (k_learn_samples_cols_jobs) and learns its tree level by level with the statistics kernels, all jobs of a
+// chunk in the same rounds; chunks of at most a quarter of the free device memory.  The result does not depend on the chunking.
+// *stat_bytes_d2h: bytes of root histograms, shortlists and record slices copied to the host
+int learn_trees_gpu(std::vector<LearnTreeJob> &jobs, uint64_t *stat_bytes_d2h);
+// The same for one sample set that is already in device memory as row-major rows (fuifgpu_learn_tree, where = 1); the rows are not written
+int learn_tree_rows_gpu(const int32_t *rows_device, const uint8_t *bucket_device, int64_t n_samples, int nprops, const LearnParams &prm,
+                        std::vector<LearnNode> &nodes);
 
 // grow-only device buffers of one encode call
 struct EncScratch {

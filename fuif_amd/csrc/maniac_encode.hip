@@ -29,6 +29,9 @@
 //                every group of a picture whose channels live only on the device (fuifgpu_encode_images_device) -- the same property code as
 //                k_enc_model (enc_props_and_guess), so the learner sees what the coder will see.  The batch path's first wall times, with and
 //                without the planes crossing PCIe, are in profiles/device_resident_encode.txt.
+//   k_learn_samples_cols_jobs / k_learn_root_hist / k_learn_stats / k_learn_shortlist / k_learn_partition (and k_learn_transpose)
+//                tree_mode 2: the same samples as columns, which stay on the device, and the integer statistics of the level-wise tree learner
+//                (csrc/tree_learn.h) -- one round per tree level for all learning groups of a call; profiles/gpu_tree_learner.txt.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -428,6 +431,471 @@ int learn_samples_jobs_gpu(const std::vector<LearnJob> &jobs, LearnSamples &out)
     out.n_words = words;
     ECHK(hipMemcpy(out.raw.data(), arena + head, result, hipMemcpyDeviceToHost));   // synchronises with the null stream's kernels
 #undef ECHK
+    hipFree(arena);
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The level-wise tree learner's statistics (tree_mode 2; the host side, the record formats and the margin are in csrc/tree_learn.h).
+// The device supplies exact integers -- minimum, maximum, order statistics, conditional histograms, the partition -- and a shortlist
+// chosen with its own double log2, which is an approximation only: every decision is taken by the host's cost().
+//
+// Layout: the samples of a learning group are nprops columns of n_samples words; a node is a segment idx[lo, lo + n) of sample numbers
+// (level 0: the identity, no array).  A (node, property) scan reads the n sample numbers of the segment (contiguous) and gathers n words
+// from ONE column (n_samples * 4 bytes, 240 KB at the default sample of 60 000: a gather inside a cache-resident run, where the row-major
+// rows of tree_mode 1 would give 4 useful bytes per row of 4 * nprops).  Per level and group the statistics kernel reads at most
+// nprops * passes * 9 bytes per sample of the level's active nodes, passes = 2 + ceil(bits(max - min) / 8) <= 6; nodes of at most 4096
+// samples are staged in LDS by the first pass and read from global memory once (9 bytes per sample and property).
+
+// the same sampling as k_learn_samples_jobs, written as columns: lane s writes word s of every column (a wavefront's stores to one
+// column are one contiguous run)
+__global__ __launch_bounds__(256) void k_learn_samples_cols_jobs(const LearnJobDev *jobs, const uint32_t *first_block, int n_jobs) {
+    const uint32_t blk = blockIdx.x;
+    int lo = 0, hi = n_jobs - 1;
+    while (lo < hi) {                       // the last job whose first block is <= blk
+        const int mid = (lo + hi + 1) >> 1;
+        if (first_block[mid] <= blk) lo = mid; else hi = mid - 1;
+    }
+    const LearnJobDev &j = jobs[lo];
+    const int64_t s = (int64_t)(blk - first_block[lo]) * 256 + threadIdx.x;
+    if (s >= j.n_samples) return;
+    const int64_t i = s * j.stride;         // < w * h: n_samples = ceil(w * h / stride)
+    int32_t p[kMaxProps];
+    const int d = j.g.plane[i] - enc_props_and_guess(j.g, i, p);
+    for (int k = 0; k < j.nprops; k++) j.props[(int64_t)k * j.n_samples + s] = p[k];   // nprops = 2 * nrefs + 13 <= 63 (checked by the host)
+    j.bucket[s] = (uint8_t)(d == 0 ? 0 : e_ilog2((uint32_t)e_iabs(d)) + 1);
+}
+
+// rows [sample][nprops] -> columns [prop][sample] (fuifgpu_learn_tree on rows that are already in device memory)
+__global__ __launch_bounds__(256) void k_learn_transpose(const int32_t *rows, int32_t *cols, int64_t n_samples, int nprops) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_samples * nprops) return;
+    const int64_t p = e / n_samples, s = e - p * n_samples;
+    cols[e] = rows[s * nprops + p];
+}
+
+namespace {
+DEV int learn_bucket(const uint8_t *bucket, int64_t s) { const int b = bucket[s]; return b < kLearnBuckets ? b : kLearnBuckets - 1; }   // (a caller's byte above 16 must not leave the histogram)
+}
+
+// one block per job: the histogram of all its samples (the roots; every other node's histogram is known to the host from its parent's split)
+__global__ __launch_bounds__(256) void k_learn_root_hist(const LearnTreeJobDev *jobs, int32_t *hist) {
+    __shared__ int s_h[kLearnBuckets];
+    const LearnTreeJobDev &j = jobs[blockIdx.x];
+    const int tid = threadIdx.x;
+    if (tid < kLearnBuckets) s_h[tid] = 0;
+    __syncthreads();
+    for (int64_t i = tid; i < j.n_samples; i += 256) atomicAdd(&s_h[learn_bucket(j.bucket, i)], 1);
+    __syncthreads();
+    if (tid < kLearnBuckets) hist[(int64_t)blockIdx.x * kLearnBuckets + tid] = s_h[tid];
+}
+
+// One block per (node, property), the nodes' blocks numbered through (first_block[k] = first block = first record of node k): minimum and
+// maximum; the three order statistics k = n * q / 4 by an exact radix selection on (value - minimum) as an unsigned number, 8 bits a pass,
+// all three in the same passes; the clamped, de-duplicated candidates in the host learner's order; per candidate the histogram of the
+// samples above it.  src: -1 = the segment is the identity (level 0), else the idx buffer the level reads.
+constexpr int kLearnStage = 4096;   // samples of a node that fit the block's LDS staging
+__global__ __launch_bounds__(256) void k_learn_stats(const LearnTreeJobDev *jobs, const LearnNodeDesc *nodes, const uint32_t *first_block, int n_nodes, int src,
+                                                     LearnRec *recs) {
+    __shared__ int32_t s_v[kLearnStage];
+    __shared__ uint8_t s_b[kLearnStage];
+    __shared__ int s_h[4][3][256];          // digit histograms, one copy per wavefront of the block (fewer collisions on a few hot bins)
+    __shared__ int s_hg[4][3][kLearnBuckets + 1];
+    __shared__ int s_mn, s_mx, s_nc;
+    __shared__ uint32_t s_pre[3], s_rank[3];
+    __shared__ int32_t s_cand[3];
+    const uint32_t blk = blockIdx.x;
+    int a = 0, z = n_nodes - 1;
+    while (a < z) {                         // the last node whose first block is <= blk
+        const int mid = (a + z + 1) >> 1;
+        if (first_block[mid] <= blk) a = mid; else z = mid - 1;
+    }
+    const LearnNodeDesc &nd = nodes[a];
+    const LearnTreeJobDev &j = jobs[nd.job];
+    const int p = (int)(blk - first_block[a]);
+    const int tid = threadIdx.x, wv = tid >> 6;
+    const int n = nd.n;
+    const int32_t *col = j.cols + (int64_t)p * j.n_samples;
+    const int32_t *idx = src < 0 ? nullptr : (src ? j.idx1 : j.idx0) + nd.lo;
+    const bool staged = n <= kLearnStage;
+    LearnRec &rec = recs[blk];
+    if (tid == 0) { s_mn = 0x7FFFFFFF; s_mx = (int)0x80000000; }
+    __syncthreads();
+    int mn = 0x7FFFFFFF, mx = (int)0x80000000;
+    for (int i = tid; i < n; i += 256) {
+        const int64_t s = idx ? idx[i] : nd.lo + i;
+        const int v = col[s];
+        mn = v < mn ? v : mn; mx = v > mx ? v : mx;
+        if (staged) { s_v[i] = v; s_b[i] = (uint8_t)learn_bucket(j.bucket, s); }
+    }
+    if (mn <= mx) { atomicMin(&s_mn, mn); atomicMax(&s_mx, mx); }
+    __syncthreads();
+    mn = s_mn; mx = s_mx;
+    if (mn == mx || n < 1) {                // (uniform over the block) a constant property has no candidate
+        if (tid == 0) { rec.mn = mn; rec.mx = mx; rec.nc = 0; rec.pad = 0; }
+        return;
+    }
+    const uint32_t span = (uint32_t)mx - (uint32_t)mn;     // exact for any two int32
+    const int bits = 32 - __builtin_clz(span);               // span >= 1
+    if (tid < 3) { s_pre[tid] = 0; s_rank[tid] = (uint32_t)((uint64_t)n * (uint64_t)(tid + 1) / 4); }
+    for (int shift = ((bits + 7) / 8 - 1) * 8; shift >= 0; shift -= 8) {
+        for (int k = tid; k < 4 * 3 * 256; k += 256) (&s_h[0][0][0])[k] = 0;
+        __syncthreads();
+        const bool first = shift + 8 >= bits;                // no digit above this one: every sample takes part
+        const int up = first ? 0 : shift + 8;                 // (<= 24)
+        const uint32_t pre0 = s_pre[0], pre1 = s_pre[1], pre2 = s_pre[2];
+        for (int i = tid; i < n; i += 256) {
+            const int v = staged ? s_v[i] : col[idx ? idx[i] : nd.lo + i];
+            const uint32_t u = (uint32_t)v - (uint32_t)mn;
+            const uint32_t hi = first ? 0u : u >> up;
+            const int dg = (int)((u >> shift) & 255u);
+            if (hi == pre0) atomicAdd(&s_h[wv][0][dg], 1);
+            if (hi == pre1) atomicAdd(&s_h[wv][1][dg], 1);
+            if (hi == pre2) atomicAdd(&s_h[wv][2][dg], 1);
+        }
+        __syncthreads();
+        if (tid < 3) {                      // the digit that holds rank s_rank[tid] among the samples under the prefix
+            uint32_t rank = s_rank[tid], cum = 0;
+            int dg = 0;
+            for (; dg < 255; dg++) {
+                const uint32_t c = (uint32_t)(s_h[0][tid][dg] + s_h[1][tid][dg] + s_h[2][tid][dg] + s_h[3][tid][dg]);
+                if (cum + c > rank) break;
+                cum += c;
+            }
+            s_rank[tid] = rank - cum;
+            s_pre[tid] = (s_pre[tid] << 8) | (uint32_t)dg;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        int nc = 0;
+        for (int q = 0; q < 3; q++) {
+            int s = (int)((uint32_t)mn + s_pre[q]);
+            if (s >= mx) s = mx - 1;
+            if (s < mn) s = mn;
+            bool dup = false;
+            for (int t = 0; t < nc; t++) dup |= (s_cand[t] == s);
+            if (!dup) s_cand[nc++] = s;
+        }
+        s_nc = nc;
+    }
+    for (int k = tid; k < 4 * 3 * (kLearnBuckets + 1); k += 256) (&s_hg[0][0][0])[k] = 0;
+    __syncthreads();
+    const int nc = s_nc;
+    const int c0 = s_cand[0], c1 = nc > 1 ? s_cand[1] : 0x7FFFFFFF, c2 = nc > 2 ? s_cand[2] : 0x7FFFFFFF;   // (no value is above INT32_MAX)
+    for (int i = tid; i < n; i += 256) {
+        int v, b;
+        if (staged) { v = s_v[i]; b = s_b[i]; }
+        else { const int64_t s = idx ? idx[i] : nd.lo + i; v = col[s]; b = learn_bucket(j.bucket, s); }
+        if (v > c0) atomicAdd(&s_hg[wv][0][b], 1);
+        if (v > c1) atomicAdd(&s_hg[wv][1][b], 1);
+        if (v > c2) atomicAdd(&s_hg[wv][2][b], 1);
+    }
+    __syncthreads();
+    if (tid < 3 * kLearnBuckets) {
+        const int t = tid / kLearnBuckets, b = tid - t * kLearnBuckets;
+        const int h = s_hg[0][t][b] + s_hg[1][t][b] + s_hg[2][t][b] + s_hg[3][t][b];
+        rec.c[t].hg[b] = t < nc ? h : 0;
+        if (t < nc) atomicAdd(&s_hg[0][t][kLearnBuckets], h);     // the side's size
+    }
+    __syncthreads();
+    if (tid < 3) { rec.c[tid].s = tid < nc ? s_cand[tid] : 0; rec.c[tid].ng = tid < nc ? s_hg[0][tid][kLearnBuckets] : 0; }
+    if (tid == 0) { rec.mn = mn; rec.mx = mx; rec.nc = nc; rec.pad = 0; }
+}
+
+namespace {
+DEV double learn_cost(const int32_t *hist, int n) {   // Learner::cost with the device's log2: an approximation, used for the shortlist only
+    if (n <= 0) return 0.0;
+    double c = 0.0;
+    for (int b = 0; b < kLearnBuckets; b++) if (hist[b]) c -= hist[b] * log2((double)hist[b] / n);
+    return c;
+}
+}  // namespace
+
+// One wavefront per node: the approximate gain of every valid candidate, then (lane 0, in property / candidate order) the shortlist
+__global__ __launch_bounds__(64) void k_learn_shortlist(const LearnNodeDesc *nodes, const uint32_t *first_block, const LearnRec *recs, LearnShort *shorts) {
+    __shared__ double s_gain[3 * kMaxProps];
+    __shared__ int s_valid[3 * kMaxProps];
+    const LearnNodeDesc &nd = nodes[blockIdx.x];
+    const uint32_t fb = first_block[blockIdx.x];
+    int nprops = (int)(first_block[blockIdx.x + 1] - fb);
+    nprops = nprops < kMaxProps ? nprops : kMaxProps;
+    const int n = nd.n;
+    const double parent = learn_cost(nd.hist, n);
+    for (int c = threadIdx.x; c < 3 * nprops; c += 64) {
+        const int p = c / 3, t = c - 3 * p;
+        const LearnRec &rec = recs[fb + p];
+        int valid = 0;
+        double gain = 0.0;
+        if (t < rec.nc) {
+            const LearnCand &cd = rec.c[t];
+            if (cd.ng >= nd.min_leaf && n - cd.ng >= nd.min_leaf) {
+                int32_t hl[kLearnBuckets];
+                for (int b = 0; b < kLearnBuckets; b++) hl[b] = nd.hist[b] - cd.hg[b];
+                gain = parent - learn_cost(cd.hg, cd.ng) - learn_cost(hl, n - cd.ng);
+                valid = 1;
+            }
+        }
+        s_gain[c] = gain; s_valid[c] = valid;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    LearnShort &sh = shorts[blockIdx.x];
+    double best = 0.0;
+    bool any = false;
+    for (int c = 0; c < 3 * nprops; c++)
+        if (s_valid[c] && (!any || s_gain[c] > best)) { best = s_gain[c]; any = true; }
+    const double floor_gain = best - (double)n * kLearnMargin;
+    int count = 0, overflow = 0;
+    for (int c = 0; c < 3 * nprops && any; c++) {
+        if (!s_valid[c] || s_gain[c] < floor_gain) continue;
+        if (count == kLearnShortCap) { overflow = 1; break; }
+        const int p = c / 3, t = c - 3 * p;
+        const LearnCand &cd = recs[fb + p].c[t];
+        LearnShortEntry &e = sh.e[count++];
+        e.prop = p; e.s = cd.s; e.ng = cd.ng;
+        for (int b = 0; b < kLearnBuckets; b++) e.hg[b] = cd.hg[b];
+    }
+    sh.count = count; sh.overflow = overflow;
+}
+
+// One block per node that splits: the stable partition of its segment, the ng samples with prop > s first, into the other idx buffer
+__global__ __launch_bounds__(256) void k_learn_partition(const LearnTreeJobDev *jobs, const LearnSplitDesc *splits, int src) {
+    __shared__ int s_scan[2][256];
+    const LearnSplitDesc sp = splits[blockIdx.x];
+    const LearnTreeJobDev &j = jobs[sp.job];
+    const int32_t *col = j.cols + (int64_t)sp.prop * j.n_samples;
+    const int32_t *in = src < 0 ? nullptr : (src ? j.idx1 : j.idx0) + sp.lo;
+    int32_t *out = (src == 0 ? j.idx1 : j.idx0) + sp.lo;
+    const int tid = threadIdx.x;
+    int base_gt = 0, base_le = 0;
+    for (int i0 = 0; i0 < sp.n; i0 += 256) {
+        const int i = i0 + tid;
+        int s = 0, flag = 0;
+        if (i < sp.n) { s = in ? in[i] : sp.lo + i; flag = col[s] > sp.s ? 1 : 0; }
+        int cur = 0;
+        s_scan[0][tid] = flag;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {   // inclusive scan of the 256 flags
+            s_scan[cur ^ 1][tid] = s_scan[cur][tid] + (tid >= d ? s_scan[cur][tid - d] : 0);
+            cur ^= 1;
+            __syncthreads();
+        }
+        const int incl = s_scan[cur][tid], total = s_scan[cur][255];
+        if (i < sp.n) {
+            const int pos = flag ? base_gt + incl - 1 : sp.ng + base_le + (tid - incl);
+            if (pos >= 0 && pos < sp.n) out[pos] = s;   // (ng is the count of the same comparison: always inside)
+        }
+        const int chunk = sp.n - i0 < 256 ? sp.n - i0 : 256;
+        base_gt += total; base_le += chunk - total;
+        __syncthreads();
+    }
+}
+
+namespace {
+// the kernels as the provider of a level's statistics (csrc/tree_learn.h); the jobs' device table is the caller's
+struct GpuLearnProvider : LearnStatsProvider {
+    const LearnTreeJobDev *d_jobs = nullptr;
+    std::vector<int> nprops;                 // per job
+    int src = -1;                            // the idx buffer the next round reads (-1: the identity)
+    uint64_t stat_bytes = 0;
+    uint8_t *d_nodes = nullptr, *d_recs = nullptr, *d_shorts = nullptr, *d_splits = nullptr;
+    size_t cap_nodes = 0, cap_recs = 0, cap_shorts = 0, cap_splits = 0;
+    std::vector<uint32_t> first;
+
+    ~GpuLearnProvider() override { hipFree(d_nodes); hipFree(d_recs); hipFree(d_shorts); hipFree(d_splits); }
+    static int grow(uint8_t *&p, size_t &cap, size_t want) {
+        if (want <= cap) return FUIFGPU_OK;
+        hipFree(p); p = nullptr; cap = 0;
+        want += want / 2;
+        if (hipMalloc((void **)&p, want) != hipSuccess) return FUIFGPU_E_HIP;
+        cap = want;
+        return FUIFGPU_OK;
+    }
+    int root_hists(std::vector<int32_t> &hist) override {
+        const size_t nj = nprops.size();
+        hist.assign(nj * kLearnBuckets, 0);
+        if (!nj) return FUIFGPU_OK;
+        int32_t *d = nullptr;
+        if (hipMalloc((void **)&d, hist.size() * sizeof(int32_t)) != hipSuccess) return FUIFGPU_E_HIP;
+        hipLaunchKernelGGL(k_learn_root_hist, dim3((unsigned)nj), dim3(256), 0, nullptr, d_jobs, d);
+        int rc = hipGetLastError() == hipSuccess ? FUIFGPU_OK : FUIFGPU_E_HIP;
+        if (rc == FUIFGPU_OK && hipMemcpy(hist.data(), d, hist.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = FUIFGPU_E_HIP;
+        stat_bytes += hist.size() * sizeof(int32_t);
+        hipFree(d);
+        return rc;
+    }
+    int level(const std::vector<LearnNodeDesc> &nodes, std::vector<LearnShort> &shorts) override {
+        const size_t nn = nodes.size();
+        shorts.assign(nn, LearnShort());
+        if (!nn) return FUIFGPU_OK;
+        first.assign(nn + 1, 0);
+        uint64_t blocks = 0;
+        for (size_t k = 0; k < nn; k++) {
+            if (nodes[k].job < 0 || (size_t)nodes[k].job >= nprops.size()) return FUIFGPU_E_ARG;
+            first[k] = (uint32_t)blocks; blocks += (uint64_t)nprops[(size_t)nodes[k].job];
+        }
+        first[nn] = (uint32_t)blocks;
+        if (blocks > 0x7FFFFFFFull || nn > 0x7FFFFFFFull) return FUIFGPU_E_ARG;
+        const size_t off_first = (sizeof(LearnNodeDesc) * nn + 255) / 256 * 256, head = off_first + sizeof(uint32_t) * (nn + 1);
+        int rc = grow(d_nodes, cap_nodes, head);
+        if (rc == FUIFGPU_OK) rc = grow(d_recs, cap_recs, sizeof(LearnRec) * (size_t)blocks);
+        if (rc == FUIFGPU_OK) rc = grow(d_shorts, cap_shorts, sizeof(LearnShort) * nn);
+        if (rc != FUIFGPU_OK) return rc;
+        std::vector<uint8_t> host(head, 0);
+        memcpy(host.data(), nodes.data(), sizeof(LearnNodeDesc) * nn);
+        memcpy(host.data() + off_first, first.data(), sizeof(uint32_t) * (nn + 1));
+        if (hipMemcpy(d_nodes, host.data(), head, hipMemcpyHostToDevice) != hipSuccess) return FUIFGPU_E_HIP;
+        const LearnNodeDesc *dn = reinterpret_cast<const LearnNodeDesc *>(d_nodes);
+        const uint32_t *df = reinterpret_cast<const uint32_t *>(d_nodes + off_first);
+        hipLaunchKernelGGL(k_learn_stats, dim3((unsigned)blocks), dim3(256), 0, nullptr, d_jobs, dn, df, (int)nn, src, reinterpret_cast<LearnRec *>(d_recs));
+        hipLaunchKernelGGL(k_learn_shortlist, dim3((unsigned)nn), dim3(64), 0, nullptr, dn, df, reinterpret_cast<const LearnRec *>(d_recs),
+                           reinterpret_cast<LearnShort *>(d_shorts));
+        if (hipGetLastError() != hipSuccess) return FUIFGPU_E_HIP;
+        if (hipMemcpy(shorts.data(), d_shorts, sizeof(LearnShort) * nn, hipMemcpyDeviceToHost) != hipSuccess) return FUIFGPU_E_HIP;   // synchronises
+        stat_bytes += sizeof(LearnShort) * nn;
+        return FUIFGPU_OK;
+    }
+    int full_slice(size_t node, std::vector<LearnRec> &recs) override {
+        if (node + 1 >= first.size()) return FUIFGPU_E_ARG;
+        recs.assign((size_t)(first[node + 1] - first[node]), LearnRec());
+        if (recs.empty()) return FUIFGPU_OK;
+        if (hipMemcpy(recs.data(), d_recs + sizeof(LearnRec) * (size_t)first[node], sizeof(LearnRec) * recs.size(), hipMemcpyDeviceToHost) != hipSuccess) return FUIFGPU_E_HIP;
+        stat_bytes += sizeof(LearnRec) * recs.size();
+        return FUIFGPU_OK;
+    }
+    int partition(const std::vector<LearnSplitDesc> &splits) override {
+        if (!splits.empty()) {
+            const int rc = grow(d_splits, cap_splits, sizeof(LearnSplitDesc) * splits.size());
+            if (rc != FUIFGPU_OK) return rc;
+            if (hipMemcpy(d_splits, splits.data(), sizeof(LearnSplitDesc) * splits.size(), hipMemcpyHostToDevice) != hipSuccess) return FUIFGPU_E_HIP;
+            hipLaunchKernelGGL(k_learn_partition, dim3((unsigned)splits.size()), dim3(256), 0, nullptr, d_jobs, reinterpret_cast<const LearnSplitDesc *>(d_splits), src);
+            if (hipGetLastError() != hipSuccess) return FUIFGPU_E_HIP;
+        }
+        src = src == 0 ? 1 : 0;
+        return FUIFGPU_OK;
+    }
+};
+
+size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+
+// jobs[a, b) in one arena: [LearnTreeJobDev][LearnJobDev][first blocks][per job: columns, buckets, idx0, idx1]
+int learn_trees_chunk(std::vector<LearnTreeJob> &jobs, size_t a, size_t b, uint64_t *stat_bytes) {
+    const size_t nj = b - a;
+    const size_t off_sample = up256(sizeof(LearnTreeJobDev) * nj), off_first = off_sample + up256(sizeof(LearnJobDev) * nj);
+    const size_t head = off_first + up256(sizeof(uint32_t) * (nj + 1));
+    size_t total = head;
+    std::vector<size_t> off_cols(nj), off_bucket(nj), off_idx(nj);
+    std::vector<uint8_t> host(head, 0);
+    uint32_t *first = reinterpret_cast<uint32_t *>(host.data() + off_first);
+    uint64_t blocks = 0;
+    for (size_t k = 0; k < nj; k++) {
+        const LearnJob &j = jobs[a + k].sample;
+        const int64_t npix = (int64_t)j.g.w * j.g.h;
+        if (!j.g.plane || j.g.w < 1 || j.g.h < 1 || j.g.nrefs < 0 || j.g.nrefs > kMaxRefs || j.nprops != 2 * j.g.nrefs + kNonRefProps || j.stride < 1 ||
+            j.n_samples != (npix + j.stride - 1) / j.stride || j.n_samples > 0x7FFFFFFF)
+            return FUIFGPU_E_ARG;
+        const size_t n = (size_t)j.n_samples;
+        off_cols[k] = total; total += up256(n * (size_t)j.nprops * sizeof(int32_t));
+        off_bucket[k] = total; total += up256(n);
+        off_idx[k] = total; total += 2 * up256(n * sizeof(int32_t));
+        first[k] = (uint32_t)blocks; blocks += ((uint64_t)n + 255) / 256;
+    }
+    first[nj] = (uint32_t)blocks;
+    if (blocks > 0x7FFFFFFFull) return FUIFGPU_E_ARG;
+    uint8_t *arena = nullptr;
+    if (hipMalloc((void **)&arena, total) != hipSuccess) return FUIFGPU_E_HIP;
+    LearnTreeJobDev *h_tree = reinterpret_cast<LearnTreeJobDev *>(host.data());
+    LearnJobDev *h_sample = reinterpret_cast<LearnJobDev *>(host.data() + off_sample);
+    GpuLearnProvider gp;
+    std::vector<LevelJob> lj(nj);
+    for (size_t k = 0; k < nj; k++) {
+        const LearnTreeJob &j = jobs[a + k];
+        const size_t n = (size_t)j.sample.n_samples;
+        LearnJobDev &d = h_sample[k];
+        d.g = j.sample.g; d.n_samples = j.sample.n_samples; d.stride = j.sample.stride; d.nprops = j.sample.nprops; d.pad = 0;
+        d.props = reinterpret_cast<int32_t *>(arena + off_cols[k]);
+        d.bucket = arena + off_bucket[k];
+        LearnTreeJobDev &t = h_tree[k];
+        t.cols = d.props; t.bucket = d.bucket;
+        t.idx0 = reinterpret_cast<int32_t *>(arena + off_idx[k]);
+        t.idx1 = reinterpret_cast<int32_t *>(arena + off_idx[k] + up256(n * sizeof(int32_t)));
+        t.n_samples = j.sample.n_samples; t.nprops = j.sample.nprops; t.pad = 0;
+        gp.nprops.push_back(j.sample.nprops);
+        lj[k].n_samples = j.sample.n_samples; lj[k].nprops = j.sample.nprops; lj[k].prm = j.prm;
+    }
+    int rc = hipMemcpy(arena, host.data(), head, hipMemcpyHostToDevice) == hipSuccess ? FUIFGPU_OK : FUIFGPU_E_HIP;
+    if (rc == FUIFGPU_OK && blocks) {
+        hipLaunchKernelGGL(k_learn_samples_cols_jobs, dim3((unsigned)blocks), dim3(256), 0, nullptr, reinterpret_cast<const LearnJobDev *>(arena + off_sample),
+                           reinterpret_cast<const uint32_t *>(arena + off_first), (int)nj);
+        if (hipGetLastError() != hipSuccess) rc = FUIFGPU_E_HIP;
+    }
+    if (rc == FUIFGPU_OK) {
+        gp.d_jobs = reinterpret_cast<const LearnTreeJobDev *>(arena);
+        rc = learn_levelwise(lj, gp);
+    }
+    if (rc == FUIFGPU_OK) for (size_t k = 0; k < nj; k++) jobs[a + k].nodes.swap(lj[k].nodes);
+    if (stat_bytes) *stat_bytes += gp.stat_bytes;
+    if (hipDeviceSynchronize() != hipSuccess && rc == FUIFGPU_OK) rc = FUIFGPU_E_HIP;   // nothing of the chunk runs once its arena goes
+    hipFree(arena);
+    return rc;
+}
+}  // namespace
+
+int learn_trees_gpu(std::vector<LearnTreeJob> &jobs, uint64_t *stat_bytes_d2h) {
+    if (stat_bytes_d2h) *stat_bytes_d2h = 0;
+    if (jobs.empty()) return FUIFGPU_OK;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return FUIFGPU_E_HIP;
+    const size_t budget = free_b / 4;   // a chunk is a run of consecutive jobs; every tree is learned on its own, so the chunking changes no result
+    // samples, buckets, the two idx buffers; the records of a level (at most n / (2 * min_leaf) active nodes of nprops records) on top
+    auto bytes_of = [](const LearnTreeJob &j) {
+        const size_t n = (size_t)(j.sample.n_samples > 0 ? j.sample.n_samples : 0), np = (size_t)(j.sample.nprops > 0 ? j.sample.nprops : 0);
+        const size_t leaf = (size_t)(j.prm.min_leaf > 0 ? j.prm.min_leaf : 1);
+        return n * (4 * np + 9) + (n / (2 * leaf) + 1) * (np * sizeof(LearnRec) + sizeof(LearnShort));
+    };
+    for (size_t a = 0; a < jobs.size();) {
+        size_t b = a + 1, sum = bytes_of(jobs[a]);
+        while (b < jobs.size() && sum + bytes_of(jobs[b]) <= budget) sum += bytes_of(jobs[b++]);
+        const int rc = learn_trees_chunk(jobs, a, b, stat_bytes_d2h);
+        if (rc != FUIFGPU_OK) return rc;
+        a = b;
+    }
+    return FUIFGPU_OK;
+}
+
+int learn_tree_rows_gpu(const int32_t *rows_device, const uint8_t *bucket_device, int64_t n_samples, int nprops, const LearnParams &prm,
+                        std::vector<LearnNode> &nodes) {
+    nodes.assign(1, LearnNode());
+    if (n_samples < 0 || n_samples > 0x7FFFFFFF || nprops < 1 || nprops >= kMaxProps) return FUIFGPU_E_ARG;
+    if (n_samples == 0) return FUIFGPU_OK;
+    if (!rows_device || !bucket_device) return FUIFGPU_E_ARG;
+    const size_t n = (size_t)n_samples;
+    const size_t off_cols = up256(sizeof(LearnTreeJobDev)), off_idx = off_cols + up256(n * (size_t)nprops * sizeof(int32_t));
+    const size_t total = off_idx + 2 * up256(n * sizeof(int32_t));
+    uint8_t *arena = nullptr;
+    if (hipMalloc((void **)&arena, total) != hipSuccess) return FUIFGPU_E_HIP;
+    LearnTreeJobDev t;
+    t.cols = reinterpret_cast<int32_t *>(arena + off_cols); t.bucket = bucket_device;
+    t.idx0 = reinterpret_cast<int32_t *>(arena + off_idx); t.idx1 = reinterpret_cast<int32_t *>(arena + off_idx + up256(n * sizeof(int32_t)));
+    t.n_samples = n_samples; t.nprops = nprops; t.pad = 0;
+    int rc = hipMemcpy(arena, &t, sizeof(t), hipMemcpyHostToDevice) == hipSuccess ? FUIFGPU_OK : FUIFGPU_E_HIP;
+    const uint64_t blocks = ((uint64_t)n * (uint64_t)nprops + 255) / 256;
+    if (blocks > 0x7FFFFFFFull) rc = FUIFGPU_E_ARG;
+    if (rc == FUIFGPU_OK) {
+        hipLaunchKernelGGL(k_learn_transpose, dim3((unsigned)blocks), dim3(256), 0, nullptr, rows_device, reinterpret_cast<int32_t *>(arena + off_cols), n_samples, nprops);
+        if (hipGetLastError() != hipSuccess) rc = FUIFGPU_E_HIP;
+    }
+    if (rc == FUIFGPU_OK) {
+        GpuLearnProvider gp;
+        gp.d_jobs = reinterpret_cast<const LearnTreeJobDev *>(arena);
+        gp.nprops.push_back(nprops);
+        std::vector<LevelJob> lj(1);
+        lj[0].n_samples = n_samples; lj[0].nprops = nprops; lj[0].prm = prm;
+        rc = learn_levelwise(lj, gp);
+        if (rc == FUIFGPU_OK) nodes.swap(lj[0].nodes);
+    }
+    if (hipDeviceSynchronize() != hipSuccess && rc == FUIFGPU_OK) rc = FUIFGPU_E_HIP;
     hipFree(arena);
     return rc;
 }

@@ -639,79 +639,8 @@ inline int props_and_guess(int32_t *p, const Chan &c, const std::vector<RefInfo>
     }
 }
 
-// ---- the writer's own tree learner --------------------------------------------------------------
-// Greedy top-down splits on a pixel sample.  Cost of a sample set = n * H(bucket) where bucket is
-// the zero/exponent class of the residual (what the adaptive zero/exp chances have to learn); a
-// split is kept when it saves more than `threshold` bits (scaled by the sampling stride).
-struct Sample { int32_t bucket; };
-struct Learner {
-    int nprops;
-    std::vector<int32_t> props;   // [sample][nprops]
-    std::vector<uint8_t> bucket;  // [sample]
-    double scale = 1.0;           // pixels represented by one sample
-    int max_nodes = 4095, max_depth = 14, min_leaf = 48;
-    // leaf_params: the slope of the description-length rule, set so that 4K photographic streams cost the decoder as many
-    // tree steps per symbol as the reference encoder's own output for the same images (9.8-9.9 both); a flat 16-bit bar,
-    // the rule until round 2, gave 11.1 steps per symbol, trees a third larger and files 0.1 % LARGER (sample-fitted splits)
-    double threshold_bits = 0.0, leaf_params = 11.5;
-    struct LNode { int prop = -1, split = 0, gt = -1, le = -1; };
-    std::vector<LNode> nodes;
-
-    static double cost(const int *hist, int n) {
-        if (n <= 0) return 0.0;
-        double c = 0.0;
-        for (int b = 0; b < 17; b++) if (hist[b]) c -= hist[b] * std::log2((double)hist[b] / n);
-        return c;
-    }
-    void build(std::vector<int> &idx, int lo, int hi, int node, int depth) {
-        const int n = hi - lo;
-        if (n < 2 * min_leaf || depth >= max_depth || (int)nodes.size() + 2 > max_nodes) return;
-        int hist[17] = {0};
-        for (int i = lo; i < hi; i++) hist[bucket[idx[i]]]++;
-        const double parent = cost(hist, n);
-        // what a split has to save: a flat number of bits, or (threshold_bits <= 0) the description length of the extra leaf,
-        // (k/2) log2(pixels of the node) for the k chances it has to learn from those pixels
-        const double bar = threshold_bits > 0.0 ? threshold_bits : 0.5 * leaf_params * std::log2((double)n * scale);
-        if (parent * scale < bar) return;
-        double best_gain = 0.0; int best_p = -1, best_s = 0;
-        std::vector<int32_t> vals(n);
-        for (int p = 0; p < nprops; p++) {
-            int mn = 0x7FFFFFFF, mx = (int)0x80000000;
-            for (int i = 0; i < n; i++) { int v = props[(size_t)idx[lo + i] * nprops + p]; vals[i] = v; mn = std::min(mn, v); mx = std::max(mx, v); }
-            if (mn == mx) continue;
-            int cands[3]; int nc = 0;
-            for (int qd = 1; qd <= 3; qd++) {
-                size_t k = (size_t)n * qd / 4;
-                std::nth_element(vals.begin(), vals.begin() + k, vals.end());
-                int s = vals[k];
-                if (s >= mx) s = mx - 1;
-                if (s < mn) s = mn;
-                bool dup = false;
-                for (int t = 0; t < nc; t++) dup |= (cands[t] == s);
-                if (!dup) cands[nc++] = s;
-            }
-            for (int t = 0; t < nc; t++) {
-                const int s = cands[t];
-                int hg[17] = {0}; int ng = 0;
-                for (int i = lo; i < hi; i++) if (props[(size_t)idx[i] * nprops + p] > s) { hg[bucket[idx[i]]]++; ng++; }
-                if (ng < min_leaf || n - ng < min_leaf) continue;
-                int hl[17];
-                for (int b = 0; b < 17; b++) hl[b] = hist[b] - hg[b];
-                double gain = parent - cost(hg, ng) - cost(hl, n - ng);
-                if (gain > best_gain) { best_gain = gain; best_p = p; best_s = s; }
-            }
-        }
-        if (best_p < 0 || best_gain * scale < bar) return;
-        int mid = (int)(std::partition(idx.begin() + lo, idx.begin() + hi, [&](int i) { return props[(size_t)i * nprops + best_p] > best_s; }) - idx.begin());
-        nodes[node].prop = best_p; nodes[node].split = best_s;
-        int g = (int)nodes.size(); nodes.push_back(LNode());
-        int l = (int)nodes.size(); nodes.push_back(LNode());
-        nodes[node].gt = g; nodes[node].le = l;
-        build(idx, lo, mid, g, depth + 1);
-        build(idx, mid, hi, l, depth + 1);
-    }
-};
-
+// ---- the writer's own tree learner: csrc/tree_learn.h (Learner, the recursive host learner of tree_mode 1, and learn_levelwise, the
+// level-wise one of tree_mode 2 whose statistics come from the kernels of maniac_encode.hip) --------------------------------------------
 struct GroupCoder {
     const uint16_t *tree_table, *pixel_table;
     int max_properties, tree_mode, max_tree_nodes, split_bits;
@@ -721,11 +650,17 @@ struct GroupCoder {
     // device-only channels: the learner's samples of the picture's groups as k_learn_samples_jobs computed them, sample_job[channel] = job or -1
     const LearnSamples *samples = nullptr;
     const std::vector<int> *sample_job = nullptr;
+    // tree_mode 2: the trees of the picture's groups as the level-wise learner left them (learn_trees_device), learned[channel]; a channel
+    // that learns nothing has no entry
+    const std::vector<std::vector<LearnNode>> *learned = nullptr;
 };
 
 // bytes of whole planes / channels the current encode call of this thread has moved (fuifgpu_encode_plane_traffic): every copy of
 // channel samples between host and device goes through these two
 thread_local uint64_t g_plane_h2d = 0, g_plane_d2h = 0;
+// what the tree learner of the current encode call has brought to the host (fuifgpu_encode_learn_traffic): sample rows and buckets
+// (tree_mode 1 on device-only channels), shortlists and record slices of the level statistics (tree_mode 2)
+thread_local uint64_t g_learn_sample_d2h = 0, g_learn_stat_d2h = 0;
 int plane_upload(int32_t *dev, const int32_t *host, size_t samples) {
     g_plane_h2d += sizeof(int32_t) * samples;
     return fuifgpu_dev_upload(dev, host, sizeof(int32_t) * samples);
@@ -752,7 +687,7 @@ struct LearnPlan {
 LearnPlan plan_learner(const Chan &c, int tree_mode, int max_tree_nodes) {
     LearnPlan lp;
     const size_t npix = (size_t)c.w * c.h;
-    if (tree_mode != 1 || npix < 4096) return lp;
+    if ((tree_mode != 1 && tree_mode != 2) || npix < 4096) return lp;   // 2: learned exactly as 1, the statistics on the GPU
     // sample pixels on a coprime stride so every row/column phase is seen
     size_t target = 60000;
     if (max_tree_nodes > 4095) {
@@ -866,7 +801,10 @@ size_t encode_group(Bytes &io, Image &img, int ci, int predictor, bool compress,
         L.max_depth = lp.max_depth; L.min_leaf = lp.min_leaf;
         L.nprops = nprops; L.scale = (double)stride; L.max_nodes = gc.max_tree_nodes;
         L.threshold_bits = (double)gc.split_bits;
-        if (c.resident()) {   // the same rows, in the same order, from the device
+        if (gc.tree_mode == 2) {   // learned before the pictures' groups were written, all groups of the call in the same rounds
+            if (gc.learned && (size_t)ci < gc.learned->size() && !(*gc.learned)[(size_t)ci].empty()) L.nodes = (*gc.learned)[(size_t)ci];
+            else { L.nodes.assign(1, Learner::LNode()); if (gc.gpu_rc && *gc.gpu_rc == FUIFGPU_OK) *gc.gpu_rc = FUIFGPU_E_HIP; }   // (no host route behind it)
+        } else if (c.resident()) {   // the same rows, in the same order, from the device
             const int job = gc.samples && gc.sample_job ? (*gc.sample_job)[(size_t)ci] : -1;
             if (job < 0) { if (gc.gpu_rc && *gc.gpu_rc == FUIFGPU_OK) *gc.gpu_rc = FUIFGPU_E_HIP; }
             else {
@@ -880,10 +818,12 @@ size_t encode_group(Bytes &io, Image &img, int ci, int predictor, bool compress,
             L.props.insert(L.props.end(), props.begin(), props.end());
             L.bucket.push_back((uint8_t)(d == 0 ? 0 : ilog2u((uint32_t)iabs(d)) + 1));
         }
-        std::vector<int> idx(L.bucket.size());
-        for (size_t i = 0; i < idx.size(); i++) idx[i] = (int)i;
-        L.nodes.assign(1, Learner::LNode());
-        L.build(idx, 0, (int)idx.size(), 0, 0);
+        if (gc.tree_mode != 2) {
+            std::vector<int> idx(L.bucket.size());
+            for (size_t i = 0; i < idx.size(); i++) idx[i] = (int)i;
+            L.nodes.assign(1, Learner::LNode());
+            L.build(idx, 0, (int)idx.size(), 0, 0);
+        }
         if (L.nodes.size() > 1) use = &L;
     }
     std::vector<TNode> tree;
@@ -946,6 +886,9 @@ int write_stream(Image &img, int nch, int bit_depth, bool squeezed, const fuifgp
 
 static int squeeze_quantize_and_fetch(fuifgpu::Image &img, const fuifgpu_encode_options &o, const fuifgpu::Lossy &lossy, bool colour_option, bool on_gpu,
                                       bool keep_resident, bool &squeezed, int rc);
+static int encode_images_common(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
+                                const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette, uint8_t **blobs_out, size_t *sizes_out,
+                                bool device_input, const fuifgpu_animation_options *anim_options);
 
 // planes -> Image with the CLI's default forward transforms applied (fuif.cpp:380-455) and, with a quality, its Quantize (fuif.cpp:459-503),
 // on the host or on the GPU.  device_input: `planes` is device memory -- the forward transforms run on working copies there (gpu_forward is
@@ -1103,6 +1046,40 @@ int fuifgpu_encode_plane_traffic(uint64_t *h2d_bytes, uint64_t *d2h_bytes) {
     return FUIFGPU_OK;
 }
 
+int fuifgpu_encode_learn_traffic(uint64_t *sample_bytes_d2h, uint64_t *stat_bytes_d2h) {
+    if (sample_bytes_d2h) *sample_bytes_d2h = g_learn_sample_d2h;
+    if (stat_bytes_d2h) *stat_bytes_d2h = g_learn_stat_d2h;
+    return FUIFGPU_OK;
+}
+
+// the tree learner on its own: one sample set through the recursive host learner, the level-wise learner with the kernels' statistics, or
+// the level-wise learner with the plain C++ statistics
+int fuifgpu_learn_tree(const int32_t *props, const uint8_t *bucket, int64_t n_samples, int nprops, const fuifgpu_learn_options *opt, int where,
+                       fuifgpu_learn_node *nodes_out, int cap, int *n_nodes) {
+    if (n_samples < 0 || n_samples > INT32_MAX || nprops < 1 || nprops >= kMaxProps || where < 0 || where > 2 || !nodes_out || cap < 1 || !n_nodes ||
+        (n_samples > 0 && (!props || !bucket)))
+        return FUIFGPU_E_ARG;
+    LearnParams q;
+    if (opt) {
+        if (opt->struct_size < sizeof(fuifgpu_learn_options)) return FUIFGPU_E_ARG;
+        q.max_nodes = opt->max_nodes; q.max_depth = opt->max_depth; q.min_leaf = opt->min_leaf;
+        q.threshold_bits = (double)(opt->split_bits > 0 ? opt->split_bits : 0); q.scale = opt->scale;
+    }
+    if (q.max_nodes < 1 || q.max_depth < 0 || q.min_leaf < 1 || !(q.scale > 0.0) || !std::isfinite(q.scale)) return FUIFGPU_E_ARG;
+    if (where != 1)
+        for (int64_t i = 0; i < n_samples; i++) if (bucket[i] > 16) return fail_with_message(FUIFGPU_E_ARG, "learn_tree: a residual class above 16");
+    std::vector<LearnNode> nodes;
+    int rc = FUIFGPU_OK;
+    if (where == 0) learn_tree_recursive(props, bucket, n_samples, nprops, q, nodes);
+    else if (where == 2) rc = learn_tree_levelwise_host(props, bucket, n_samples, nprops, q, nodes);
+    else rc = learn_tree_rows_gpu(props, bucket, n_samples, nprops, q, nodes);
+    if (rc != FUIFGPU_OK) return rc;
+    if (nodes.size() > (size_t)cap) return fail_with_message(FUIFGPU_E_ARG, "learn_tree: the tree has more nodes than nodes_out holds");
+    for (size_t k = 0; k < nodes.size(); k++) nodes_out[k] = fuifgpu_learn_node{nodes[k].prop, nodes[k].split, nodes[k].gt, nodes[k].le};
+    *n_nodes = (int)nodes.size();
+    return FUIFGPU_OK;
+}
+
 int fuifgpu_quantization_constant(float quality, float chroma_quality, int squeeze_option, int chroma_table, int shift) {
     Lossy l;
     if (shift < 0 || !read_qualities(quality, chroma_quality, l)) return -FUIFGPU_E_ARG;
@@ -1123,8 +1100,11 @@ int fuifgpu_encode_animation(const int32_t *planes, int w, int h, int nch, int b
     if (o.max_properties < 0 || o.max_properties > 2 * kMaxRefs) return FUIFGPU_E_ARG;
     if (o.max_tree_nodes < 1) o.max_tree_nodes = 4095;
     if (o.max_tree_nodes > kMaxNodes) o.max_tree_nodes = kMaxNodes;
+    // tree_mode 2 learns with the batch writer's rounds: a batch of one picture, which writes the same bytes (include/fuifgpu.h)
+    if (o.tree_mode == 2) return encode_images_common(&planes, 1, w, h, nch, bit_depth, opt, lossy, palette, blob_out, size_out, false, anim_options);
 
     g_plane_h2d = g_plane_d2h = 0;
+    g_learn_sample_d2h = g_learn_stat_d2h = 0;
     Image img;
     bool squeezed = false;
     const int rc = build_transformed_image(planes, w, h, nch, bit_depth, o, l, pal, anim, img, squeezed);
@@ -1161,6 +1141,7 @@ int fuifgpu_encode_channels(const fuifgpu_raw_channel *channels, int n_channels,
     if (o.max_tree_nodes < 1) o.max_tree_nodes = 4095;
     if (o.max_tree_nodes > kMaxNodes) o.max_tree_nodes = kMaxNodes;
     g_plane_h2d = g_plane_d2h = 0;
+    g_learn_sample_d2h = g_learn_stat_d2h = 0;
     Image img;
     img.w = w; img.h = h; img.maxval = (1 << bit_depth) - 1; img.nb_channels = nb_channels;
     img.ch.resize(n_channels);
@@ -1244,7 +1225,42 @@ int learn_samples_device(Image &img, bool squeezed, const GroupCoder &gc, LearnS
         sample_job[(size_t)i] = (int)jobs.size();
         jobs.push_back(job);
     }
-    return learn_samples_jobs_gpu(jobs, out);
+    const int rc = learn_samples_jobs_gpu(jobs, out);
+    g_learn_sample_d2h += out.raw.size() * sizeof(int32_t);
+    return rc;
+}
+// tree_mode 2: the trees of every learning group of every picture of the call.  Host-resident channels go to the device here, one phase
+// earlier than for the GPU pixel loop (the same copies); the samples are computed there and stay there.  learned[m][channel]
+int learn_trees_device(std::vector<Image> &imgs, const std::vector<char> &squeezed, const GroupCoder &gc, std::vector<std::vector<std::vector<LearnNode>>> &learned) {
+    std::vector<LearnTreeJob> jobs;
+    std::vector<std::pair<size_t, int>> where;
+    learned.assign(imgs.size(), std::vector<std::vector<LearnNode>>());
+    for (size_t m = 0; m < imgs.size(); m++) {
+        Image &img = imgs[m];
+        learned[m].resize(img.ch.size());
+        for (int i = 0; i < (int)img.ch.size(); i++) {
+            Chan &c = img.ch[i];
+            if (!c.w || !c.h || c.minval == c.maxval) continue;
+            const LearnPlan lp = plan_learner(c, gc.tree_mode, gc.max_tree_nodes);
+            if (!lp.stride) continue;
+            c.setzero();
+            std::vector<Range> ranges; std::vector<RefInfo> refs;
+            LearnTreeJob job;
+            job.sample.nprops = init_properties(ranges, refs, img, i, i, gc.max_properties);
+            job.sample.n_samples = (int64_t)lp.n_samples; job.sample.stride = (int64_t)lp.stride;
+            job.prm.max_nodes = gc.max_tree_nodes; job.prm.max_depth = lp.max_depth; job.prm.min_leaf = lp.min_leaf;
+            job.prm.threshold_bits = (double)gc.split_bits; job.prm.scale = (double)lp.stride;
+            const int rc = build_enc_group(c, refs, group_predictor(img, i, squeezed[m] != 0, false), job.sample.g);
+            if (rc != FUIFGPU_OK) return rc;
+            where.push_back(std::make_pair(m, i));
+            jobs.push_back(std::move(job));
+        }
+    }
+    uint64_t stat_bytes = 0;
+    const int rc = learn_trees_gpu(jobs, &stat_bytes);
+    g_learn_stat_d2h += stat_bytes;
+    for (size_t k = 0; k < jobs.size() && rc == FUIFGPU_OK; k++) learned[where[k].first][(size_t)where[k].second].swap(jobs[k].nodes);
+    return rc;
 }
 // encoding/encoding.cpp:455-470: the fixed header fields into `head`, the transform list into `io`
 void begin_stream(const Image &img, int nch, int bit_depth, const fuifgpu_encode_options &o, Bytes &head, Bytes &io) {
@@ -1300,6 +1316,8 @@ int finish_stream(Bytes &head, const Bytes &io, int responsive[5], std::vector<G
 
 int write_stream(Image &img, int nch, int bit_depth, bool squeezed, const fuifgpu_encode_options &o, uint8_t **blob_out, size_t *size_out,
                  bool dct_style) {
+    if (o.tree_mode == 2)   // (fuifgpu_encode_channels; every other entry point takes tree_mode 2 to the batch writer)
+        return fail_with_message(FUIFGPU_E_UNSUPPORTED, "tree_mode 2 (trees learned with GPU statistics) is not offered for channels in a transform domain: use tree_mode 1");
     EncScratch enc_scratch;
     struct DevCleanup {   // device copies of the channels and the coder's buffers live as long as this call
         Image &img; EncScratch &s;
@@ -1368,9 +1386,19 @@ int write_streams_batch(std::vector<Image> &imgs, int nch, int bit_depth, const 
     build_chance_table(tables.data(), 0xFFFFFFFFu / 19, 2);
     build_chance_table(tables.data() + 8192, 0x0d000000u, 6);
     GroupCoder gc{tables.data(), tables.data() + 8192, o.max_properties, o.tree_mode, o.max_tree_nodes, o.split_bits > 0 ? o.split_bits : 0};
+    if (o.tree_mode == 2) {   // no silent host route: without a device the call fails whatever the pictures hold
+        int n_devices = 0;
+        const int rc = fuifgpu_device_count(&n_devices);
+        if (rc != FUIFGPU_OK) return rc;
+    }
     int gpu_rc = channel_ranges(imgs.data(), imgs.size());
     if (gpu_rc != FUIFGPU_OK) return gpu_rc;
     gc.gpu_rc = &gpu_rc;
+    std::vector<std::vector<std::vector<LearnNode>>> learned;
+    if (gc.tree_mode == 2) {
+        const int rc = learn_trees_device(imgs, squeezed, gc, learned);
+        if (rc != FUIFGPU_OK) return rc;
+    }
     std::vector<EncJob> jobs;
     std::vector<std::vector<PendingGroup>> pending(imgs.size());
     for (size_t m = 0; m < imgs.size(); m++) {
@@ -1378,9 +1406,10 @@ int write_streams_batch(std::vector<Image> &imgs, int nch, int bit_depth, const 
         responsive_downscales(img, squeezed[m] != 0, false);
         LearnSamples samples;
         std::vector<int> sample_job;
-        const int rc = learn_samples_device(img, squeezed[m] != 0, gc, samples, sample_job);
+        const int rc = gc.tree_mode == 2 ? FUIFGPU_OK : learn_samples_device(img, squeezed[m] != 0, gc, samples, sample_job);
         if (rc != FUIFGPU_OK) return rc;
         gc.samples = &samples; gc.sample_job = &sample_job;
+        gc.learned = gc.tree_mode == 2 ? &learned[m] : nullptr;
         for (int i = 0; i < (int)img.ch.size(); i++) {
             Chan &c = img.ch[i];
             if (!c.w || !c.h) continue;
@@ -1395,7 +1424,7 @@ int write_streams_batch(std::vector<Image> &imgs, int nch, int bit_depth, const 
             }
             pending[m].push_back(std::move(pg));
         }
-        gc.samples = nullptr; gc.sample_job = nullptr;
+        gc.samples = nullptr; gc.sample_job = nullptr; gc.learned = nullptr;
     }
     if (gpu_rc != FUIFGPU_OK) return gpu_rc;
     int rc = maniac_encode_jobs_gpu(jobs, gc.pixel_table);
@@ -1446,7 +1475,7 @@ int write_streams_batch(std::vector<Image> &imgs, int nch, int bit_depth, const 
 // the batch entry points: planes[m] on the host, or (device_input) in device memory
 static int encode_images_common(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
                                 const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette, uint8_t **blobs_out, size_t *sizes_out,
-                                bool device_input, const fuifgpu_animation_options *anim_options = nullptr) {
+                                bool device_input, const fuifgpu_animation_options *anim_options) {
     if (!planes || !blobs_out || !sizes_out || n_images < 1 || w < 1 || h < 1 || nch < 1 || nch > 8 || bit_depth < 1 || bit_depth > 14) return FUIFGPU_E_ARG;
     fuifgpu_encode_options o;
     Lossy l;
@@ -1460,6 +1489,7 @@ static int encode_images_common(const int32_t *const *planes, int n_images, int 
     for (int m = 0; m < n_images; m++) { blobs_out[m] = nullptr; sizes_out[m] = 0; }
     for (int m = 0; m < n_images; m++) if (!planes[m]) return FUIFGPU_E_ARG;
     g_plane_h2d = g_plane_d2h = 0;
+    g_learn_sample_d2h = g_learn_stat_d2h = 0;
     std::vector<Image> imgs((size_t)n_images);
     std::vector<char> squeezed((size_t)n_images, 0);
     int rc = FUIFGPU_OK;
@@ -1478,12 +1508,12 @@ static int encode_images_common(const int32_t *const *planes, int n_images, int 
 }
 extern "C" int fuifgpu_encode_images_lossy(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth,
                                            const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out) {
-    return encode_images_common(planes, n_images, w, h, nch, bit_depth, opt, lossy, nullptr, blobs_out, sizes_out, false);
+    return encode_images_common(planes, n_images, w, h, nch, bit_depth, opt, lossy, nullptr, blobs_out, sizes_out, false, nullptr);
 }
 extern "C" int fuifgpu_encode_images_ex(const int32_t *const *planes, int planes_on_device, int n_images, int w, int h, int nch, int bit_depth,
                                         const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette,
                                         uint8_t **blobs_out, size_t *sizes_out) {
-    return encode_images_common(planes, n_images, w, h, nch, bit_depth, opt, lossy, palette, blobs_out, sizes_out, planes_on_device != 0);
+    return encode_images_common(planes, n_images, w, h, nch, bit_depth, opt, lossy, palette, blobs_out, sizes_out, planes_on_device != 0, nullptr);
 }
 extern "C" int fuifgpu_encode_animations(const int32_t *const *frames, int on_device, int n_clips, int w, int frame_h, int nch, int bit_depth,
                                          const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette,
@@ -1496,7 +1526,7 @@ extern "C" int fuifgpu_encode_images(const int32_t *const *planes, int n_images,
 }
 extern "C" int fuifgpu_encode_images_device(const int32_t *const *planes_device, int n_images, int w, int h, int nch, int bit_depth,
                                             const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out) {
-    return encode_images_common(planes_device, n_images, w, h, nch, bit_depth, opt, lossy, nullptr, blobs_out, sizes_out, true);
+    return encode_images_common(planes_device, n_images, w, h, nch, bit_depth, opt, lossy, nullptr, blobs_out, sizes_out, true, nullptr);
 }
 
 // ---- YUV 4:2:0 video frames: what `fuif -y WxH[:b]` writes (import/read_yuv.h:29-63, fuif.cpp:277-283, 309-329, 431-435) ------------------
@@ -1602,6 +1632,7 @@ extern "C" int fuifgpu_encode_yuv420(const void *const *frames, int on_device, i
     const bool on_gpu = on_device != 0 || o.gpu_forward != 0;
     const int den = framerate > 0 ? framerate : 10;   // fuif.cpp:335; image.h: den = 10
     g_plane_h2d = g_plane_d2h = 0;
+    g_learn_sample_d2h = g_learn_stat_d2h = 0;
     std::vector<Image> imgs((size_t)n);
     std::vector<char> squeezed((size_t)n, 0);
     auto release = [&]() { for (Image &im : imgs) for (Chan &c : im.ch) { if (c.dev) fuifgpu_dev_free(c.dev); c.dev = nullptr; } };
@@ -1648,7 +1679,7 @@ extern "C" int fuifgpu_encode_yuv420(const void *const *frames, int on_device, i
     if (rc != FUIFGPU_OK) { release(); return rc; }
     // pictures in device memory stay there until their last coded byte: the batch writer; so does a batch whose pixel loops run on the
     // GPU (one launch pair for all of them); else picture by picture through the stream writer of fuifgpu_encode_image
-    if (on_device || (o.gpu_entropy && n > 1)) rc = write_streams_batch(imgs, 3, bit_depth, squeezed, o, blobs_out, sizes_out);
+    if (on_device || (o.gpu_entropy && n > 1) || o.tree_mode == 2) rc = write_streams_batch(imgs, 3, bit_depth, squeezed, o, blobs_out, sizes_out);
     else for (int m = 0; m < n && rc == FUIFGPU_OK; m++) rc = write_stream(imgs[(size_t)m], 3, bit_depth, squeezed[(size_t)m] != 0, o, &blobs_out[m], &sizes_out[m]);
     if (rc != FUIFGPU_OK) {
         release();

@@ -304,7 +304,14 @@ int fuifgpu_fwd_quantize(int32_t *plane, int64_t n_samples, int q, int32_t *minm
  * Writes a lossless FUIF stream the reference decoder accepts, with the format decisions of the
  * reference CLI for photographic PNM input (fuif.cpp:380-455,580-588; encoding/encoding.cpp:455-573).
  * tree_mode 0 = single-leaf MANIAC trees (byte-identical to `fuif -I 0`), 1 = trees learned by the
- * writer's own greedy learner.  *blob_out is malloc'd; release with fuifgpu_free_blob. */
+ * writer's own greedy learner, 2 = learned exactly as 1 with the learner's statistics (minimum, maximum, order statistics,
+ * conditional histograms, the partition of the samples) computed by kernels, level by level for all learning groups of the call at
+ * once; every floating-point decision stays in the host code of tree_mode 1, so the bytes are those of tree_mode 1 on every entry
+ * point and option combination.  The batch entry points, fuifgpu_encode_animations and fuifgpu_encode_yuv420 honour 2 for all
+ * channels (host-resident channels go to the device before the trees are learned instead of after; the samples never come to the
+ * host); the single-picture entry points take it through the batch writer with one picture.  fuifgpu_encode_channels:
+ * FUIFGPU_E_UNSUPPORTED.  No GPU: FUIFGPU_E_HIP (no silent host route).
+ * *blob_out is malloc'd; release with fuifgpu_free_blob. */
 typedef struct {
     uint32_t struct_size;   /* = sizeof(fuifgpu_encode_options) of the CALLER's header.  The library reads that many bytes and takes
                                every field behind them as 0, so the struct can grow at its end without breaking callers built
@@ -314,7 +321,7 @@ typedef struct {
     int32_t ycocg;          /* 1: YCoCg when nch >= 3 (CLI default) */
     int32_t squeeze;        /* 1: default Squeeze (CLI default "responsive") */
     int32_t max_properties; /* CLI default 12 (-E) */
-    int32_t tree_mode;      /* 0 none, 1 learned */
+    int32_t tree_mode;      /* 0 none, 1 learned, 2 learned with the statistics on the GPU (same bytes as 1) */
     int32_t max_tree_nodes; /* cap for learned trees (<= 65535) */
     int32_t emit_index;     /* 1: append the group index trailer (see fuifgpu_index_*) */
     int32_t split_bits;     /* learned trees: > 0 = a split must save this many bits (flat); 0 = the default rule, the description
@@ -381,6 +388,27 @@ int fuifgpu_channel_stats(const int32_t *plane_device, int64_t n_samples, int32_
 /* diagnostic: bytes of whole sample planes/channels the LAST encode call of this thread copied host->device and device->host
  * (tables, trees, job records, learner samples, coder state and coded bytes are not planes and are not counted) */
 int fuifgpu_encode_plane_traffic(uint64_t *h2d_bytes, uint64_t *d2h_bytes);
+/* ---- the writer's tree learner on its own (found by symbol lookup: the ABI version does not change) ----
+ * One sample set: n_samples rows of nprops int32 properties, row-major, and one residual class (0..16) per sample.  where: 0 = the
+ * recursive host learner of tree_mode 1, 1 = props / bucket are DEVICE pointers (read, never written) and the tree is learned level by
+ * level with the kernels of tree_mode 2, 2 = host pointers, level by level with plain C++ statistics (a test aid: the host side of
+ * tree_mode 2 without a GPU).  All three write the same node array: nodes_out gets it in the order the host learner numbers it
+ * (node 0 the root, prop -1 a leaf, gt / le the children for property > split / <= split), *n_nodes its length (1 = a single leaf).
+ * opt NULL: max_nodes 4095, max_depth 14, min_leaf 48, split_bits 0, scale 1.  FUIFGPU_E_ARG: nprops < 1 or > 63, a negative count or
+ * one above INT32_MAX, max_nodes < 1, max_depth < 0, min_leaf < 1, a scale that is not a positive finite number, a class above 16
+ * (host pointers), or a tree of more than cap nodes. */
+typedef struct {
+    uint32_t struct_size;   /* = sizeof(fuifgpu_learn_options) */
+    int32_t max_nodes, max_depth, min_leaf;
+    int32_t split_bits;     /* as fuifgpu_encode_options::split_bits */
+    double scale;           /* pixels a sample stands for (the sampling stride) */
+} fuifgpu_learn_options;
+typedef struct { int32_t prop, split, gt, le; } fuifgpu_learn_node;
+int fuifgpu_learn_tree(const int32_t *props, const uint8_t *bucket, int64_t n_samples, int nprops, const fuifgpu_learn_options *opt,
+                       int where, fuifgpu_learn_node *nodes_out, int cap, int *n_nodes);
+/* diagnostic, per thread, of the LAST encode call: bytes of learner sample rows + classes copied to the host (tree_mode 1 on channels
+ * that live on the device), and bytes of level statistics (root histograms, shortlists, record slices) copied to the host (tree_mode 2) */
+int fuifgpu_encode_learn_traffic(uint64_t *sample_bytes_d2h, uint64_t *stat_bytes_d2h);
 /* ---- Palette and channel compaction: what the CLI tries by default for PNM input that is not a photograph (fuif.cpp:345-350, 374-430;
  * transform/palette.h:92-142) ----
  * In the CLI's order: every channel whose range has 256 values or more and whose samples use fewer than compact_pre_percent of them is
