@@ -184,8 +184,9 @@ def test_invalid_permutation_flags_the_image_and_zero_fills(gpulib, manifest):
 
 def test_wide_configuration_for_two_batches_in_flight(gpulib, manifest):
     """fuifgpu_batch_set_in_flight(2): launches with few tiles (streams without index) run the wide kernel instantiation with 20 instead of 58
-    supernodes in LDS (two wavefronts per SIMD, room for a second batch's launch) -- same planes, same bytes consumed; two such batches decode
-    side by side on two streams (where the runtime has streams: one GPU box; the emulator runs them one after the other)"""
+    supernodes in LDS (two wavefronts per SIMD, room for a second batch's launch) -- same planes, same bytes consumed.  The two batches here
+    decode one after the other: both launches go to the null stream, which serialises them.  Two such batches on two streams, side by side,
+    are tests/test_gpu_stream_order.py::test_two_batches_on_two_streams"""
     picks = [e for e in manifest["fixtures"] if e["name"] in ("c1_rgb8_512x512", "rgb8_97x61", "jpeg420_256x192_q90", "rgb8_512x384_I16_bigtrees", "rgba14_80x72")]
     assert picks
     for e in picks:
