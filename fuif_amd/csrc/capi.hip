@@ -561,7 +561,7 @@ static int stage_streams(fuifgpu_batch *b, const uint8_t *const *blobs, const si
     for (int i = 0; i < n_images; i++) {
         if (sizes[i] > 0xFFFFFFF0ull) return FUIFGPU_E_ARG;
         int src = -1;
-        for (auto &sp : seen) if (sp.first == blobs[i] && b->jobs[sp.second].blob_size == sizes[i]) { src = sp.second; break; }
+        for (auto &sp : seen) if (sp.first == blobs[i] && sizes[sp.second] == sizes[i]) { src = sp.second; break; }
         size_t padded = (sizes[i] + 15) / 16 * 16 + 16;
         if (off + padded + 256 > b->blob_cap) { g_last_error = "blob capacity exceeded"; return FUIFGPU_E_NOMEM; }  // the last 256-byte read window stays inside the allocation
         StreamJob &j = b->jobs[i];
@@ -569,9 +569,15 @@ static int stage_streams(fuifgpu_batch *b, const uint8_t *const *blobs, const si
             int r = parse_and_plan(blobs[i], sizes[i], tmp, b->plan.keep);   // (the batch's own keep: the signatures of two schedule lengths differ)
             if (r != FUIFGPU_OK) { g_last_error = tmp.message; return r; }
             if (tmp.signature != b->plan.signature) { g_last_error = "image " + std::to_string(i) + " has a different geometry/transform chain"; return FUIFGPU_E_MISMATCH; }
+            // A valid trailer stands BEHIND the stream (include/fuifgpu.h): the stream ends where it begins, whether its groups are used or not.
+            // A whole file never reads that far; a file that was cut and given an index afterwards ends at the cut (truncated), it does not
+            // go on into the trailer's bytes as if they were picture data.
             std::vector<GroupEntry> idx;
-            if (b->group_parallel) parse_index_trailer(blobs[i], sizes[i], tmp.data_start, nch, idx, nullptr);
+            size_t stream_end = sizes[i];
+            if (!parse_index_trailer(blobs[i], sizes[i], tmp.data_start, nch, idx, &stream_end)) stream_end = sizes[i];
+            if (!b->group_parallel) idx.clear();
             if (idx.empty()) idx.push_back(GroupEntry{(uint32_t)tmp.data_start, 0});
+            j.blob_size = (uint32_t)stream_end;
             groups.push_back(std::move(idx));
             group_of[i] = (int)groups.size() - 1;
             HIPCHK(hipMemsetAsync(b->d_blobs + off + (padded - 32), 0, 32, st));
@@ -583,9 +589,10 @@ static int stage_streams(fuifgpu_batch *b, const uint8_t *const *blobs, const si
             HIPCHK(hipMemcpyAsync(b->d_blobs + off, b->d_blobs + b->jobs[src].blob_off, padded, hipMemcpyDeviceToDevice, st));
             j.data_start = b->jobs[src].data_start;
             j.limit = b->jobs[src].limit;
+            j.blob_size = b->jobs[src].blob_size;
             group_of[i] = group_of[src];
         }
-        j.blob_off = off; j.blob_size = (uint32_t)sizes[i];
+        j.blob_off = off;
         j.flags = 0;
         off += padded;
     }

@@ -322,3 +322,125 @@ CASES = [
 
 def build(case):
     return case["make"](**case["args"])
+
+
+# ---- streams whose every prefix is decoded (tests/test_gpu_prefixes.py on the kernels, tests/test_oracle_vs_ref.py on the oracle) ----------
+# Small on purpose: a sweep decodes one prefix per byte.  `length` = the range the test asserts for a stream the product's writer makes from
+# a seeded picture (the bytes follow the writer, the seed is fixed); golden files have the length the manifest records.
+# The writer learns no MANIAC tree for a channel below 4096 pixels (writer.cpp, plan_learner), so at 40 x 30 tree_mode 1 and 0 write the same
+# bytes, single-leaf trees throughout -- and a predictor-0 group with a single-leaf tree takes the kernel's "fast track" (leaf_symbol on every
+# symbol), not the chunk-fast / fast_symbol_hw / leaf_symbol hand-overs.  Those run where a predictor-0 group has a tree: in the writer's
+# 128 x 64 stream below (the smallest picture whose last Squeeze residual has 4096 pixels; its tree has over 100 nodes) and in the reference
+# encoder's gray8_64x48 (3 nodes).  Both were checked once against a library whose window reload was edited away (188u -> 260u): it decodes
+# the large channels of exactly these streams wrongly, and every other stream of the list as before.
+def golden_stream(name):
+    import os
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", name + ".fuif"), "rb") as f:
+        return f.read()
+
+
+def _written(w, h, channels, bits, sigma=None, **keywords):
+    import fuif_amd
+    from .synth import photographic
+    keywords.setdefault("split_bits", 2)
+    return fuif_amd.encode_image(photographic(w, h, channels, bits, sigma=sigma), bits, **keywords)
+
+
+def rolled_back_picture(w=40, h=30, seed=5):
+    """uniform noise in the even columns, a constant in the odd ones: the residuals of the first horizontal Squeeze steps are uniform over a
+    power-of-two range, which MANIAC codes in more bits than the flat code of an "uncompressed" group, so the writer rolls the largest
+    groups back (encoding.cpp:545-551) -- the shape `fuif -U` forces"""
+    a = np.random.default_rng(seed).integers(0, 256, size=(3, h, w)).astype(np.int32)
+    a[:, :, 1::2] = 128
+    return a
+
+
+def _rolled_back():
+    import fuif_amd
+    return fuif_amd.encode_image(rolled_back_picture(), 8, ycocg=False, tree_mode=1, split_bits=2)
+
+
+def _jpeg420(w, h):
+    from .jpeglike import encode_jpeg_like
+    from .synth import photographic
+    return encode_jpeg_like(photographic(w, h, 3, 8, seed=77, sigma=1.0), 90, True)
+
+
+PREFIX_STREAMS = [
+    # YCoCg + Squeeze, lossless, predictor 0 in every residual group, 22 groups
+    dict(name="writer_trees_40x30", make=lambda: _written(40, 30, 3, 8, tree_mode=1), length=(2900, 3300)),
+    dict(name="writer_notrees_40x30", make=lambda: _written(40, 30, 3, 8, tree_mode=0), length=(2900, 3300)),
+    # learned trees from the product's writer in front of predictor-0 symbols: one channel, Squeeze, the 64 x 64 residual learns
+    dict(name="writer_trees_128x64", make=lambda: _written(128, 64, 1, 8, tree_mode=1, sigma=0.3), length=(3300, 3700)),
+    # groups of 300 and 600 pixels stored "uncompressed" between compressed ones
+    dict(name="writer_rolled_back_40x30", make=_rolled_back, length=(3500, 3900)),
+    # a non-zero predictor in every group (reference CLI, -P 7 -R 0): no fast path at all.  The smallest -P fixture with more than 9 pixels
+    dict(name="rgb8_65x34_P7_nosqueeze", make=lambda: golden_stream("rgb8_65x34_P7_nosqueeze"), length=(5334, 5334)),
+    # 14 bits without YCoCg: 31-chance leaves, the wide context format
+    dict(name="writer_wide14_32x24", make=lambda: _written(32, 24, 4, 14, ycocg=False, tree_mode=1), length=(4600, 5200)),
+    # more than 31 properties: kPropPitchWide, half chunks
+    dict(name="writer_props24_40x30", make=lambda: _written(40, 30, 4, 8, max_properties=24, tree_mode=1), length=(3800, 4300)),
+    # the DCT shape: 192 channels.  8 x 8 is the smallest picture the transcode-like writer takes (one pixel per channel, every group
+    # "uncompressed": a group start and a rac_init every four bytes); 64 x 48 has compressed groups among them
+    dict(name="jpeg420_8x8", make=lambda: _jpeg420(8, 8), length=(650, 800)),
+    dict(name="jpeg420_64x48", make=lambda: _jpeg420(64, 48), length=(1800, 2200)),
+    # written by the real reference, with its learned trees: Squeeze only, and YCoCg + Squeeze + Quantization + Approximate
+    dict(name="gray8_64x48", make=lambda: golden_stream("gray8_64x48"), length=(2066, 2066)),
+    dict(name="approx_quant_rgb8_40x30", make=lambda: golden_stream("approx_quant_rgb8_40x30"), length=(484, 484)),
+    # YCoCg without Squeeze: three groups of one channel, the median predictor, each channel a property of the next (the bare form of
+    # PREFIX_INDEXED_WAITING below)
+    dict(name="writer_nosqueeze_40x30", make=lambda: _written(40, 30, 3, 8, squeeze=False, tree_mode=1), length=(2800, 3250)),
+]
+# the stream of the group-parallel sweep: the first one, written with the group index
+PREFIX_INDEXED = dict(name="writer_trees_40x30_indexed", make=lambda: _written(40, 30, 3, 8, tree_mode=1, index=True), length=(2950, 3400))
+# Its single-leaf predictor-0 groups take the kernel's fast track, which never looks at another channel's rows: its tiles never wait and
+# are never suspended, and the fast symbol decoders do not run in them.  Two more streams with the index:
+# * the 128 x 64 stream: the fast symbol decoders and their hand-overs inside tiles.  Its tiles look at the rows of the channels they refer
+#   to, but every such channel is half the size of the tile's own and started no later: it stays ahead, and no suspension was ever counted;
+# * the 40 x 30 picture without Squeeze: three tiles of one channel each, all of one size, channel k a property of channel k + 1, so a
+#   tile runs into the rows its neighbour has not finished, and is suspended and resumed (the position travels in the tile record).  How
+#   often depends on which wavefront gets there first: 7 to 20 suspensions per sweep were counted on the emulator with four wavefronts
+PREFIX_INDEXED_TREES = dict(name="writer_trees_128x64_indexed", make=lambda: _written(128, 64, 1, 8, tree_mode=1, sigma=0.3, index=True), length=(3330, 3760))
+PREFIX_INDEXED_WAITING = dict(name="writer_nosqueeze_40x30_indexed", make=lambda: _written(40, 30, 3, 8, squeeze=False, tree_mode=1, index=True), length=(2820, 3290))
+# (indexed stream, the same stream without the trailer)
+PREFIX_SIDE_INDEX = [(PREFIX_INDEXED, PREFIX_STREAMS[0]), (PREFIX_INDEXED_TREES, PREFIX_STREAMS[2]), (PREFIX_INDEXED_WAITING, PREFIX_STREAMS[-1])]
+assert PREFIX_STREAMS[2]["name"] == "writer_trees_128x64" and PREFIX_STREAMS[-1]["name"] == "writer_nosqueeze_40x30"
+# (golden fixture, preview): the preview's byte limit lies inside the stream.  approx_quant_rgb8_40x30 is the smallest fixture whose previews the
+# manifest lists; only its preview 0 has a limit of its own (byte 75).  pal_rgb_graphic_120x90 (Palette + Squeeze, 2438 bytes) has limits at
+# 271, 515 and 1171 for previews 2, 3 and 4.  rgb8_97x61 has 11 322 bytes: too many for a sweep of every byte
+PREFIX_PREVIEWS = [("approx_quant_rgb8_40x30", 0), ("pal_rgb_graphic_120x90", 3)]
+
+# (stream name, prefix length, reason): prefixes the real reference itself fails on, left out of both tests.  None: it decodes them all
+PREFIX_REFERENCE_FAILS = []
+
+_prefix_blobs = {}
+
+
+def prefix_stream(entry):
+    """the bytes of one PREFIX_STREAMS entry (made once per process), its length inside the entry's range"""
+    name = entry["name"]
+    if name not in _prefix_blobs:
+        blob = entry["make"]()
+        lo, hi = entry["length"]
+        assert lo <= len(blob) <= hi, (name, len(blob))
+        _prefix_blobs[name] = blob
+    return _prefix_blobs[name]
+
+
+def first_planned_length(blob, limit=64):
+    """the shortest prefix fuif_amd.Plan accepts (found by trying)"""
+    import fuif_amd
+    for n in range(1, limit + 1):
+        try:
+            fuif_amd.Plan(blob[:n])
+            return n
+        except fuif_amd.FuifGpuError:
+            pass
+    raise AssertionError("no prefix of up to %d bytes makes a plan" % limit)
+
+
+def side_indexed(blob, groups, n):
+    """blob[:n] with a group index of the groups that start inside it behind the cut (n beyond the first group's start).  To the reference,
+    which knows no trailer, those bytes are stream data for the group that contains the cut; to the product the stream ends at the cut"""
+    import fuif_amd
+    return fuif_amd.index_append(blob[:n], [g for g in groups if g[1] < n])

@@ -200,7 +200,7 @@ int fuifgpu_batch_sched_stats(fuifgpu_batch *batch, uint64_t *out8);
  *     payload = varint 1 ; varint n ; n x { varint channel delta ; varint byte-offset delta }
  * which the reference decoder never reads (it stops after the last group, encoding.cpp:708-717):
  * indexed files still decode with the unmodified reference.  fuifgpu_batch_upload() finds the
- * trailer by itself and then decodes every group of every image on its own wavefront; streams
+ * trailer by itself, ends the stream where the trailer begins and then decodes every group of every image on its own wavefront; streams
  * without one are decoded one wavefront per image.  Ways to get an index: the writer below
  * (emit_index), or decode once and keep fuifgpu_batch_group_index()'s result with the asset. */
 /* groups of the trailer of `blob` (n_groups = 0: none / not valid for this stream) */

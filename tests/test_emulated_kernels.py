@@ -162,6 +162,53 @@ def test_gpu_parity_tests_pass_on_the_wavefront_emulator():
     run_dealt(SELECTED, env, max(1, min(7, (os.cpu_count() or 2) - 1)))
 
 
+# tests/test_gpu_prefixes.py on the emulator: (node ids of one pytest process, FUIF_TEST_PREFIX_STRIDE, group-parallel).  On the GPU a sweep cuts
+# at every byte; here a decode takes a quarter of a second and more, so the cut moves in steps of a prime, chosen so that each process takes
+# 35 to 50 seconds: 40 to 160 cuts whose distances to the window reloads, the group starts and the row ends all differ.  The two 40 x 30
+# writer streams hold the same bytes (see fuif_amd/edgecases.py), so their two strides give two sets of cuts of one stream; the two streams
+# behind them are the ones whose predictor-0 groups have trees, where the fast symbol decoders and their hand-overs run.  The group-parallel
+# sweeps run with four emulated wavefronts at once on a library built with -DFUIF_STATS, which counts the suspended tiles: the sweep of
+# the unsqueezed stream asserts that there were some.  Their status tests share the sweep's decodes, so they ride in the same process.
+# Every other sweep of the file runs on the GPU only.
+T = "tests/test_gpu_prefixes.py::"
+PREFIX_SWEEPS = [
+    ([T + "test_every_prefix_decodes_like_the_oracle[writer_trees_40x30]"], 19, False),
+    ([T + "test_every_prefix_decodes_like_the_oracle[writer_notrees_40x30]"], 23, False),
+    ([T + "test_every_prefix_decodes_like_the_oracle[writer_trees_128x64]"], 59, False),
+    ([T + "test_every_prefix_decodes_like_the_oracle[gray8_64x48]", T + "test_the_streams_are_what_their_sweeps_are_for"], 17, False),
+    ([T + "test_every_prefix_decodes_like_the_oracle[rgb8_65x34_P7_nosqueeze]"], 157, False),
+] + [([T + "%s[%s-%s]" % (test, arena, stream) for test in ("test_every_prefix_group_parallel_equals_sequential", "test_no_status_bit_but_truncated_with_a_side_index")
+      for arena in arenas], stride, True)
+     for stream, arenas, stride in (("writer_trees_40x30_indexed", ("arenas",), 61), ("writer_trees_40x30_indexed", ("pinned",), 67),
+                                    ("writer_trees_128x64_indexed", ("arenas", "pinned"), 173), ("writer_nosqueeze_40x30_indexed", ("arenas", "pinned"), 127))]
+
+
+def test_prefix_sweeps_pass_on_the_wavefront_emulator():
+    """every entry of PREFIX_SWEEPS in a pytest process of its own (each has its own stride), all at once"""
+    if sys.platform != "linux" or os.uname().machine != "x86_64":
+        pytest.skip("the emulator's context switch is x86-64 SysV assembly")
+    lib = build_emulated_library()
+    stats_lib = build_emulated_library(extra=["-DFUIF_STATS"], name="libfuifgpu_emu_stats.so")
+    procs = []
+    for nodes, stride, group_parallel in PREFIX_SWEEPS:
+        env = dict(os.environ, FUIF_AMD_LIB=lib, EMU_ALARM="1500", FUIF_TEST_PREFIX_STRIDE=str(stride))
+        if group_parallel:   # as in test_pinned_tiles_with_concurrent_emulated_wavefronts: tiles really wait for each other
+            env.update(FUIF_AMD_LIB=stats_lib, EMU_WAVES="4", EMU_THREADS="4")
+        procs.append((nodes, subprocess.Popen([sys.executable, "-m", "pytest", "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider"] + nodes, cwd=ROOT, env=env,
+                                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
+    outs = []
+    for nodes, p in procs:
+        try:
+            out, _ = p.communicate(timeout=1700)
+        except subprocess.TimeoutExpired:
+            p.kill()
+            out, _ = p.communicate()
+            out += "\n[timed out]"
+        outs.append((nodes, p.returncode, out))
+    for nodes, rc, out in outs:
+        assert rc == 0 and "%d passed" % len(nodes) in out and "failed" not in out, "%s\n%s" % (nodes, out[-3000:])
+
+
 def test_device_selection_on_an_emulated_node_of_two_devices():
     """EMU_DEVICES=2: fuifgpu_set_device / batch_device / peer_copy between two "devices" (host memory both; the current device is
     per-thread state in the emulator as in HIP) -- a batch created on device 1 decodes there while the caller sits on device 0"""

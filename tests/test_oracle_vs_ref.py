@@ -70,3 +70,81 @@ def test_port_equals_reference_at_the_int16_edges(port, ref, case):
             wide = a0.channels[0]["data"].astype(np.int64) * case["args"]["q"]
             assert (np.abs(wide) > 32767).any()
             assert np.array_equal(a1.channels[0]["data"], np.clip(wide.astype(np.int16), 0, 16383))
+
+
+# prefixes the real reference itself fails on would stand in edgecases.PREFIX_REFERENCE_FAILS (stream name, prefix length, reason), the list
+# this test and tests/test_gpu_prefixes.py both leave out; at most 1 % of a stream's prefixes.  It is empty.
+
+
+@pytest.mark.parametrize("entry", edgecases.PREFIX_STREAMS + [p[0] for p in edgecases.PREFIX_SIDE_INDEX], ids=lambda e: e["name"])
+def test_port_equals_reference_on_every_prefix(port, ref, entry):
+    """the streams whose every prefix the kernels decode against the oracle (tests/test_gpu_prefixes.py): on each of those prefixes the
+    oracle gives what the real reference gives -- coded planes, output planes, channel ranges and geometry, FileIO semantics.  No golden
+    vector covers these cut points."""
+    blob = edgecases.prefix_stream(entry)
+    n0 = edgecases.first_planned_length(blob)
+    assert n0 < 64
+    left_out = {n for name, n, reason in edgecases.PREFIX_REFERENCE_FAILS if name == entry["name"]}
+    assert 100 * len(left_out) <= len(blob) + 1 - n0
+    failures, pairs, constructor_sized = [], 0, 0
+    for n in range(n0, len(blob) + 1):
+        if n in left_out:
+            continue
+        cut = blob[:n]
+        a0, a1 = ref.decode_both(cut, io_kind=0)
+        b0, b1 = port.decode_both(cut, io_kind=0)
+        pairs += len(b0.channels)
+        constructor_sized += sum(1 for ch in b0.channels if ch["size"] and ch["size"] != ch["w"] * ch["h"])
+        try:
+            assert a0.ok and a1.ok, "the real reference fails"
+            same(a0, b0)
+            same(a1, b1)
+        except AssertionError as e:
+            failures.append((n, str(e).split("\n")[0][:80]))
+    assert not failures, "%s: %d failing prefixes, the first: %s" % (entry["name"], len(failures), failures[:10])
+    # the planes the GPU sweep cannot compare (constructor-sized, never reached by the stream): at most a quarter of the (prefix, channel) pairs,
+    # by the oracle alone and at every byte
+    assert 4 * constructor_sized <= pairs, (entry["name"], constructor_sized, pairs)
+
+
+@pytest.mark.parametrize("name,preview", edgecases.PREFIX_PREVIEWS)
+def test_port_equals_reference_on_every_prefix_of_a_preview(port, ref, name, preview):
+    blob = edgecases.golden_stream(name)
+    failures = []
+    for n in range(edgecases.first_planned_length(blob), len(blob) + 1):
+        cut = blob[:n]
+        a0, a1 = ref.decode_both(cut, preview=preview, io_kind=0)
+        b0, b1 = port.decode_both(cut, preview=preview, io_kind=0)
+        try:
+            assert a0.ok and a1.ok, "the real reference fails"
+            same(a0, b0)
+            same(a1, b1)
+        except AssertionError as e:
+            failures.append((n, str(e).split("\n")[0][:80]))
+    assert not failures, "%s preview %d: %d failing prefixes, the first: %s" % (name, preview, len(failures), failures[:10])
+
+
+@pytest.mark.parametrize("pair", edgecases.PREFIX_SIDE_INDEX, ids=lambda p: p[0]["name"])
+def test_port_equals_reference_on_every_prefix_with_a_side_index(port, ref, pair):
+    """the byte strings of the group-parallel sweep: a prefix and, behind the cut, the index of the groups that start inside it.  The
+    reference knows no trailer: the group that contains the cut reads it as stream data, and about one in seven of these strings is refused
+    as corrupt (a channel range beyond the picture, an invalid tree).  The oracle does the same to each.  This is why the product ends a
+    stream where a valid trailer begins (capi.hip, stage_streams) and decodes such a file like the bare prefix"""
+    import fuif_amd
+    indexed = edgecases.prefix_stream(pair[0])
+    blob = edgecases.prefix_stream(pair[1])
+    groups = fuif_amd.index_parse(indexed)
+    assert indexed[: len(blob)] == blob and len(groups) >= 3
+    failures, refused = [], 0
+    for n in range(groups[0][1] + 1, len(blob) + 1):
+        side = edgecases.side_indexed(blob, groups, n)
+        a0, a1 = ref.decode_both(side, io_kind=0)
+        b0, b1 = port.decode_both(side, io_kind=0)
+        refused += not a0.ok
+        try:
+            same(a0, b0)
+            same(a1, b1)
+        except AssertionError as e:
+            failures.append((n, str(e).split("\n")[0][:80]))
+    assert not failures, "%d failing prefixes, the first: %s" % (len(failures), failures[:10])
+    assert 0 < refused < (len(blob) - groups[0][1]) // 4
