@@ -72,7 +72,7 @@ struct LearnSamples {      // every job's rows and buckets, as they came back in
     const int32_t *props(size_t job) const { return raw.data() + props_off[job]; }
     const uint8_t *bucket(size_t job) const { return reinterpret_cast<const uint8_t *>(raw.data() + n_words) + bucket_off[job]; }
 };
-// Computes what the host learner's sampling loop computes (writer.cpp encode_group) for every job, in its order.
+// Computes what the host learner's sampling loop computes (writer.cpp group_tree) for every job, in its order.
 int learn_samples_jobs_gpu(const std::vector<LearnJob> &jobs, LearnSamples &out);
 
 // ---- the level-wise tree learner's statistics on the GPU (tree_mode 2; csrc/tree_learn.h has the host side) ---------------------------------
@@ -109,6 +109,8 @@ struct EncScratch {
     uint16_t *d_table = nullptr;      // the pixel coder's chance transition table (8192 entries)
     uint32_t *d_state = nullptr;      // RacEncState + byte count + overflow flag
     void release();
+    // (release() ends by assigning a fresh EncScratch: one that holds nothing must not call it again)
+    ~EncScratch() { if (d_guess || d_leaf || d_bytes || d_tree || d_leaves || d_table || d_state) release(); }
 };
 
 // Encodes every sample of the group in row-major order with the given tree (n_nodes >= 1) into the range coder whose state is

@@ -31,11 +31,12 @@
 // earlier distance matched with an offset that was never compared -- a lossless mode that loses pixels, which is not reproduced.
 // Raw YUV 4:2:0 frames (fuifgpu_encode_yuv420, `fuif -y WxH[:b]`; import/read_yuv.h:29-63, fuif.cpp:431-435): three channels of unequal geometry
 // under a recorded [YCbCr, ChromaSubsample] pair, no colour transform, no palettes, no Matching; on the GPU routes k_unpack_yuv420 unpacks the
-// raw bytes of every frame of a call in one launch (the section at the end of this file).
+// raw bytes of every frame of a call in one launch.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "../../include/fuifgpu.h"
@@ -60,14 +61,34 @@ inline int median3(int a, int b, int c) {
     return b < c ? c : b;
 }
 
-struct Chan {
-    std::vector<int32_t> data;
+// a device buffer that goes with its owner (move-only)
+struct DevBuf {
+    void *p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { reset(); }
+    void reset() { if (p) fuifgpu_dev_free(p); p = nullptr; }   // (frees are ordered behind the kernels of the null stream)
+    bool alloc(size_t bytes) { reset(); p = fuifgpu_dev_alloc(bytes); return p != nullptr; }
+    int32_t *i32() const { return static_cast<int32_t *>(p); }
+    explicit operator bool() const { return p != nullptr; }
+};
+
+// everything of a channel but its samples
+struct ChanGeom {
     int w = 0, h = 0, minval = 0, maxval = 0, zero = 0, q = 1;
     int hshift = 0, vshift = 0, hcshift = 0, vcshift = 0, component = -1;
-    mutable int32_t *dev = nullptr;   // gpu_forward: the samples live here (w x h, contiguous) until every transform has run; gpu_entropy: a device copy of `data`
-    int64_t zeros = -1;               // number of zero samples when the statistics launch counted them (device-only channels), else -1
+    int64_t zeros = -1;               // device-only channels: the number of zero samples, counted by the statistics launch (channel_ranges)
+};
+struct Chan : ChanGeom {
+    std::vector<int32_t> data;
+    mutable DevBuf dev;               // gpu_forward: the samples live here (w x h, contiguous) until every transform has run; gpu_entropy: a device copy of `data` (ensure_dev)
     // device-only: `dev` is set and `data` is empty -- the samples never come to the host (fuifgpu_encode_images_device)
     bool resident() const { return dev && data.empty(); }
+    // a channel of the same geometry, ranges and q, without samples
+    Chan like() const { Chan g; static_cast<ChanGeom &>(g) = *this; return g; }
     void setzero() { zero = minval > 0 ? minval : (maxval < 0 ? maxval : 0); }
     void minmax() {
         int mn = 0x7FFFFFFF, mx = (int)0x80000001;
@@ -86,33 +107,33 @@ struct Bytes {
     }
 };
 
-// Range encoder matching RacInput24 (maniac/rac.h); carry handling by delayed byte + pending 0xFF run.
+// Range encoder matching RacInput24 (maniac/rac.h); carry handling by delayed byte + pending 0xFF run.  `st` is what travels to the GPU
+// pixel loop and back (maniac_encode.h)
 struct RacEnc {
     Bytes &out;
-    uint32_t range = 1u << 24, low = 0;
-    int delayed = -1;
-    int pending = 0;
+    RacEncState st{1u << 24, 0, -1, 0};
     explicit RacEnc(Bytes &o) : out(o) {}
+    RacEnc(Bytes &o, const RacEncState &behind) : out(o), st(behind) {}
     void shift() {
-        uint32_t byte = low >> 16;  // bit 8 = carry into the bytes already generated
-        if (delayed < 0) delayed = (int)byte;
-        else if (byte < 0xFF) { out.put(delayed); for (; pending; pending--) out.put(0xFF); delayed = (int)byte; }
-        else if (byte > 0xFF) { out.put(delayed + 1); for (; pending; pending--) out.put(0x00); delayed = (int)(byte & 0xFF); }
-        else pending++;
-        low = (low & 0xFFFF) << 8;
-        range <<= 8;
+        uint32_t byte = st.low >> 16;  // bit 8 = carry into the bytes already generated
+        if (st.delayed < 0) st.delayed = (int)byte;
+        else if (byte < 0xFF) { out.put(st.delayed); for (; st.pending; st.pending--) out.put(0xFF); st.delayed = (int)byte; }
+        else if (byte > 0xFF) { out.put(st.delayed + 1); for (; st.pending; st.pending--) out.put(0x00); st.delayed = (int)(byte & 0xFF); }
+        else st.pending++;
+        st.low = (st.low & 0xFFFF) << 8;
+        st.range <<= 8;
     }
     void put(uint32_t chance, int bit) {
-        if (bit) { low += range - chance; range = chance; }
-        else range -= chance;
-        while (range <= 0x10000u) shift();
+        if (bit) { st.low += st.range - chance; st.range = chance; }
+        else st.range -= chance;
+        while (st.range <= 0x10000u) shift();
     }
-    void put12(uint32_t b12, int bit) { put((((range & 0xFFFu) * b12 + 0x800u) >> 12) + ((range >> 12) * b12), bit); }
-    void putbit(int bit) { put(range >> 1, bit); }
+    void put12(uint32_t b12, int bit) { put((((st.range & 0xFFFu) * b12 + 0x800u) >> 12) + ((st.range >> 12) * b12), bit); }
+    void putbit(int bit) { put(st.range >> 1, bit); }
     // rac_enc.h:87-99: the decoder is three bytes ahead; four generated bytes, the last stays delayed
     void flush() {
-        low += 0xFFFF;
-        for (int k = 0; k < 4; k++) { range = 0xFFFF; shift(); }
+        st.low += 0xFFFF;
+        for (int k = 0; k < 4; k++) { st.range = 0xFFFF; shift(); }
     }
 };
 
@@ -174,10 +195,6 @@ void uniform_write(RacEnc &r, int min, int len, int value) {
     }
 }
 
-struct TNode {  // decoder-layout tree (maniac/compound.h:41-56)
-    int prop = -1, split = 0, child = 0, leaf = 0;
-};
-
 struct Range { int lo, hi; };
 
 struct Image {
@@ -186,7 +203,9 @@ struct Image {
     int nb_frames = 1, den = 10;   // an animation: h = nb_frames frames one above the other; den: frames per second (image.h `den`)
     std::vector<TransformDesc> transforms;
     int downscales[6];
-    bool stale_tail = false;   // write what the reference's buffer holds behind the last group (StaleTail below); the .yuv route sets it
+    bool squeezed = false;     // the default Squeeze ran (default_squeeze)
+    bool dct_style = false;    // the caller's channels were in a transform domain already (fuifgpu_encode_channels)
+    bool stale_tail = false;  // write what the reference's buffer holds behind the last group (StaleTail below); the .yuv route sets it
 };
 
 // The reference codes every group compressed first and, when that does not pay, seeks back and writes it again uncompressed
@@ -203,6 +222,39 @@ struct StaleTail {
     // what lies behind a stream of `end` bytes
     std::vector<uint8_t> behind(size_t end) const { return end < shadow.size() ? std::vector<uint8_t>(shadow.begin() + end, shadow.end()) : std::vector<uint8_t>(); }
 };
+
+// bytes of whole planes / channels the current encode call of this thread has moved (fuifgpu_encode_plane_traffic): every copy of
+// channel samples between host and device goes through plane_upload / plane_download
+thread_local uint64_t g_plane_h2d = 0, g_plane_d2h = 0;
+// what the tree learner of the current encode call has brought to the host (fuifgpu_encode_learn_traffic): sample rows and buckets
+// (tree_mode 1 on device-only channels), shortlists and record slices of the level statistics (tree_mode 2)
+thread_local uint64_t g_learn_sample_d2h = 0, g_learn_stat_d2h = 0;
+int plane_upload(int32_t *dev, const int32_t *host, size_t samples) {
+    g_plane_h2d += sizeof(int32_t) * samples;
+    return fuifgpu_dev_upload(dev, host, sizeof(int32_t) * samples);
+}
+int plane_download(int32_t *host, const int32_t *dev, size_t samples) {
+    g_plane_d2h += sizeof(int32_t) * samples;
+    return fuifgpu_dev_download(host, dev, sizeof(int32_t) * samples);
+}
+
+// a device copy of a channel's samples for the GPU pixel loop (kept until the stream is written)
+int ensure_dev(const Chan &c) {
+    if (c.dev || c.data.empty()) return FUIFGPU_OK;
+    if (!c.dev.alloc(sizeof(int32_t) * c.data.size())) return FUIFGPU_E_HIP;
+    if (c.hshift < 0) return fuifgpu_dev_upload(c.dev.p, c.data.data(), sizeof(int32_t) * c.data.size());   // a palette is a table, not a plane: not counted
+    return plane_upload(c.dev.i32(), c.data.data(), c.data.size());
+}
+
+// one k_channel_stats launch over the device planes of `who`: every channel's range and its number of zero samples
+int device_ranges(const std::vector<Chan *> &who) {
+    std::vector<StatsRec> recs;
+    for (const Chan *c : who) recs.push_back(StatsRec{c->dev.i32(), (int64_t)c->w * c->h, 0, 0});
+    std::vector<int32_t> stats(3 * recs.size());
+    const int rc = channel_stats_gpu(recs.data(), (int)recs.size(), stats.data());
+    for (size_t k = 0; k < who.size() && rc == FUIFGPU_OK; k++) { who[k]->minval = stats[3 * k]; who[k]->maxval = stats[3 * k + 1]; who[k]->zeros = stats[3 * k + 2]; }
+    return rc;
+}
 
 // ---- forward transforms ------------------------------------------------------------------------
 int smooth_tendency(int B, int a, int n) {  // transform/squeeze.h:61-77
@@ -231,17 +283,23 @@ void fwd_ycocg(Image &img) {  // transform/ycocg.h:65-95
     }
 }
 
-// transform/squeeze.h:135-170 (horizontal) / 227-263 (vertical)
-void fwd_squeeze_one(Image &img, int c, int rc, bool horizontal) {
-    const Chan in = img.ch[c];
-    Chan avg, res;
-    avg = in; res = in;
-    avg.data.clear(); res.data.clear();
+// what one Squeeze step makes of channel `in` (squeeze.h:135-146 / 227-238): the averages and the residuals, no samples yet
+void squeeze_geometry(const Chan &in, bool horizontal, Chan &avg, Chan &res) {
+    avg = in.like(); res = in.like();
     res.q = 1;
     if (horizontal) {
         avg.w = (in.w + 1) / 2; avg.h = in.h; res.w = in.w - avg.w; res.h = in.h;
         avg.hshift = in.hshift + 1; avg.hcshift = in.hcshift + 1; res.hshift = in.hshift + 1; res.hcshift = in.hcshift;
-        avg.data.assign((size_t)avg.w * avg.h, 0); res.data.assign((size_t)res.w * res.h, 0);
+    } else {
+        avg.w = in.w; avg.h = (in.h + 1) / 2; res.w = in.w; res.h = in.h - avg.h;
+        avg.vshift = in.vshift + 1; avg.vcshift = in.vcshift + 1; res.vshift = in.vshift + 1; res.vcshift = in.vcshift;
+    }
+}
+
+// the samples of that step on the host: transform/squeeze.h:147-170 (horizontal) / 239-263 (vertical)
+void squeeze_samples_host(const Chan &in, bool horizontal, Chan &avg, Chan &res) {
+    avg.data.assign((size_t)avg.w * avg.h, 0); res.data.assign((size_t)res.w * res.h, 0);
+    if (horizontal) {
         for (int y = 0; y < in.h; y++) {
             const int32_t *row = &in.data[(size_t)y * in.w];
             for (int x = 0; x < res.w; x++) {
@@ -257,9 +315,6 @@ void fwd_squeeze_one(Image &img, int c, int rc, bool horizontal) {
             if (in.w & 1) avg.data[(size_t)y * avg.w + avg.w - 1] = row[2 * (avg.w - 1)];
         }
     } else {
-        avg.w = in.w; avg.h = (in.h + 1) / 2; res.w = in.w; res.h = in.h - avg.h;
-        avg.vshift = in.vshift + 1; avg.vcshift = in.vcshift + 1; res.vshift = in.vshift + 1; res.vcshift = in.vcshift;
-        avg.data.assign((size_t)avg.w * avg.h, 0); res.data.assign((size_t)res.w * res.h, 0);
         const int w = in.w;
         for (int y = 0; y < res.h; y++) {
             for (int x = 0; x < w; x++) {
@@ -277,31 +332,26 @@ void fwd_squeeze_one(Image &img, int c, int rc, bool horizontal) {
         }
         if (in.h & 1) for (int x = 0; x < w; x++) avg.data[(size_t)(avg.h - 1) * w + x] = in.data[(size_t)(2 * (avg.h - 1)) * w + x];
     }
-    img.ch[c] = avg;
-    img.ch.insert(img.ch.begin() + rc, res);
 }
-
-// The same step with the samples on the GPU (fuifgpu_fwd_hsqueeze / fuifgpu_fwd_vsqueeze): geometry and bookkeeping as above
-int fwd_squeeze_one_gpu(Image &img, int c, int rc, bool horizontal) {
-    Chan in = img.ch[c];
-    Chan avg = in, res = in;
-    res.q = 1;
-    if (horizontal) {
-        avg.w = (in.w + 1) / 2; avg.h = in.h; res.w = in.w - avg.w; res.h = in.h;
-        avg.hshift = in.hshift + 1; avg.hcshift = in.hcshift + 1; res.hshift = in.hshift + 1; res.hcshift = in.hcshift;
-    } else {
-        avg.w = in.w; avg.h = (in.h + 1) / 2; res.w = in.w; res.h = in.h - avg.h;
-        avg.vshift = in.vshift + 1; avg.vcshift = in.vcshift + 1; res.vshift = in.vshift + 1; res.vcshift = in.vcshift;
-    }
-    avg.dev = (int32_t *)fuifgpu_dev_alloc(sizeof(int32_t) * std::max<size_t>((size_t)avg.w * avg.h, 1));
-    res.dev = (int32_t *)fuifgpu_dev_alloc(sizeof(int32_t) * std::max<size_t>((size_t)res.w * res.h, 1));
-    int rc_ = (avg.dev && res.dev) ? FUIFGPU_OK : FUIFGPU_E_HIP;
-    if (rc_ == FUIFGPU_OK)
-        rc_ = horizontal ? fuifgpu_fwd_hsqueeze(in.dev, in.w, in.h, avg.dev, res.dev, nullptr) : fuifgpu_fwd_vsqueeze(in.dev, in.w, in.h, avg.dev, res.dev, nullptr);
-    img.ch[c] = avg;
-    img.ch.insert(img.ch.begin() + rc, res);
-    fuifgpu_dev_free(in.dev);   // (frees are ordered behind the kernels of the null stream)
-    return rc_;
+// ... and on the GPU (fuifgpu_fwd_hsqueeze / fuifgpu_fwd_vsqueeze)
+int squeeze_samples_gpu(const Chan &in, bool horizontal, Chan &avg, Chan &res) {
+    const bool have = avg.dev.alloc(sizeof(int32_t) * std::max<size_t>((size_t)avg.w * avg.h, 1));
+    if (!res.dev.alloc(sizeof(int32_t) * std::max<size_t>((size_t)res.w * res.h, 1)) || !have) return FUIFGPU_E_HIP;
+    return horizontal ? fuifgpu_fwd_hsqueeze(in.dev.i32(), in.w, in.h, avg.dev.i32(), res.dev.i32(), nullptr)
+                      : fuifgpu_fwd_vsqueeze(in.dev.i32(), in.w, in.h, avg.dev.i32(), res.dev.i32(), nullptr);
+}
+// one Squeeze step of channel c: the averages take its place, the residuals go to position rc; the input, samples and device plane, goes
+// right behind the step
+int fwd_squeeze_one(Image &img, int c, int rc, bool horizontal, bool on_gpu) {
+    const Chan in = std::move(img.ch[c]);
+    Chan avg, res;
+    squeeze_geometry(in, horizontal, avg, res);
+    int err = FUIFGPU_OK;
+    if (on_gpu) err = squeeze_samples_gpu(in, horizontal, avg, res);
+    else squeeze_samples_host(in, horizontal, avg, res);
+    img.ch[c] = std::move(avg);
+    img.ch.insert(img.ch.begin() + rc, std::move(res));
+    return err;
 }
 
 std::vector<int> default_squeeze_params(const Image &img) {  // transform/squeeze.h:266-321
@@ -321,19 +371,26 @@ std::vector<int> default_squeeze_params(const Image &img) {  // transform/squeez
     return p;
 }
 
-int fwd_squeeze(Image &img, const std::vector<int> &params, bool on_gpu = false) {  // transform/squeeze.h:389-408
+int fwd_squeeze(Image &img, const std::vector<int> &params, bool on_gpu) {  // transform/squeeze.h:389-408
     for (size_t i = 0; i + 2 < params.size(); i += 3) {
         bool horizontal = params[i] & 1;
         bool in_place = !(params[i] & 2);
         int beginc = params[i + 1], endc = params[i + 2];
         int offset = in_place ? endc + 1 : img.nb_meta + img.nb_channels;
         for (int c = beginc; c <= endc; c++) {
-            if (!on_gpu) { fwd_squeeze_one(img, c, offset + c - beginc, horizontal); continue; }
-            const int rc = fwd_squeeze_one_gpu(img, c, offset + c - beginc, horizontal);
+            const int rc = fwd_squeeze_one(img, c, offset + c - beginc, horizontal, on_gpu);
             if (rc != FUIFGPU_OK) return rc;
         }
     }
     return FUIFGPU_OK;
+}
+// fuif.cpp:450-455, 576-578: the default Squeeze, unless channel[0] -- the match channel or a palette, once there is one -- is too small
+int default_squeeze(Image &img, bool on_gpu) {
+    if ((int64_t)img.ch[0].w * img.ch[0].h <= 20) return FUIFGPU_OK;
+    const int rc = fwd_squeeze(img, default_squeeze_params(img), on_gpu);
+    img.transforms.push_back({TR_SQUEEZE, {}});  // empty parameter list = "default" in the stream
+    img.squeezed = true;
+    return rc;
 }
 
 // ---- forward Palette (transform/palette.h:92-142) and the three options of the CLI that try it (fuif.cpp:374-430) -----------------
@@ -342,7 +399,6 @@ int fwd_squeeze(Image &img, const std::vector<int> &params, bool on_gpu = false)
 struct PaletteOpts {
     int colors = 0;
     float post = 0.f, pre = 0.f;
-    bool any() const { return colors > 0 || post > 0.f || pre > 0.f; }
 };
 // a tuple as one integer whose order is the order of std::set<std::vector<pixel_type>>: component 0 most significant, signed
 inline uint64_t tuple_order_key(const Chan *chans, int nb, size_t i) {
@@ -380,9 +436,9 @@ bool fwd_palette_host(Chan *chans, int nb, int limit, std::vector<int32_t> &rows
     return true;
 }
 // Image::do_transform of one Palette attempt over channels begin..end (numbered from the first non-meta channel) with at most `limit`
-// colours: on success the index replaces channel `begin`, the others go, the palette (colours x nb, hshift -1) goes in FRONT of the channel
-// list and the transform is recorded with the number of colours found; on failure nothing changes and nothing is recorded.
-// on_gpu: the samples are on the device (Chan::dev); the palette itself is a small table and lives on the host either way
+// colours: on success the index replaces channel `begin`, the others go (with their device planes), the palette (colours x nb, hshift -1)
+// goes in FRONT of the channel list and the transform is recorded with the number of colours found; on failure nothing changes and nothing
+// is recorded.  on_gpu: the samples are on the device (Chan::dev); the palette itself is a small table and lives on the host either way
 int try_palette(Image &img, int begin, int end, int limit, bool on_gpu) {
     const int bc = img.nb_meta + begin, nb = end - begin + 1;
     if (limit < 1 || nb < 1 || !img.ch[bc].w || !img.ch[bc].h) return FUIFGPU_OK;   // (the first pixel is already one colour too many)
@@ -391,12 +447,11 @@ int try_palette(Image &img, int begin, int end, int limit, bool on_gpu) {
     if (on_gpu) {
         const int32_t *planes[4] = {nullptr, nullptr, nullptr, nullptr};
         if (nb > 4) return FUIFGPU_E_ARG;
-        for (int c = 0; c < nb; c++) planes[c] = img.ch[bc + c].dev;
-        const int rc = fwd_palette_gpu(planes, nb, (int64_t)img.ch[bc].w * img.ch[bc].h, limit, img.ch[bc].dev, rows, &n_colors);
+        for (int c = 0; c < nb; c++) planes[c] = img.ch[bc + c].dev.i32();
+        const int rc = fwd_palette_gpu(planes, nb, (int64_t)img.ch[bc].w * img.ch[bc].h, limit, img.ch[bc].dev.i32(), rows, &n_colors);
         if (rc != FUIFGPU_OK) return rc;
     } else if (!fwd_palette_host(&img.ch[bc], nb, limit, rows, n_colors)) n_colors = -1;
     if (n_colors < 0) return FUIFGPU_OK;
-    for (int c = 1; c < nb; c++) { if (img.ch[bc + c].dev) fuifgpu_dev_free(img.ch[bc + c].dev); }
     img.ch.erase(img.ch.begin() + bc + 1, img.ch.begin() + bc + nb);
     Chan pal;   // Channel pch(nb_colors, nb, 0, 1); pch.hshift = -1
     pal.w = n_colors; pal.h = nb; pal.minval = 0; pal.maxval = 1; pal.hshift = -1;
@@ -410,12 +465,9 @@ int try_palette(Image &img, int begin, int end, int limit, bool on_gpu) {
 // Image::recompute_minmax for the channels the compaction heuristic looks at (the non-meta ones): host scan, or one k_channel_stats launch
 int current_ranges(Image &img, bool on_gpu) {
     if (!on_gpu) { for (int i = img.nb_meta; i < (int)img.ch.size(); i++) img.ch[i].minmax(); return FUIFGPU_OK; }
-    std::vector<StatsRec> recs;
-    for (int i = img.nb_meta; i < (int)img.ch.size(); i++) recs.push_back(StatsRec{img.ch[i].dev, (int64_t)img.ch[i].w * img.ch[i].h, 0, 0});
-    std::vector<int32_t> stats(3 * recs.size());
-    const int rc = channel_stats_gpu(recs.data(), (int)recs.size(), stats.data());
-    for (size_t k = 0; k < recs.size() && rc == FUIFGPU_OK; k++) { img.ch[img.nb_meta + k].minval = stats[3 * k]; img.ch[img.nb_meta + k].maxval = stats[3 * k + 1]; }
-    return rc;
+    std::vector<Chan *> who;
+    for (int i = img.nb_meta; i < (int)img.ch.size(); i++) who.push_back(&img.ch[i]);
+    return device_ranges(who);
 }
 // fuif.cpp:374-388 (pre: before the colour transform, ranges of 256 values and more only) and :418-430 (after it): every channel whose
 // samples use less than `fraction` of its range is compacted to the ranks of the values that occur
@@ -478,9 +530,8 @@ int fwd_match_frames(Image &img, bool on_gpu) {
     int rc = FUIFGPU_OK;
     if (on_gpu) {
         const int32_t *planes[8];
-        for (int c = 0; c < nb; c++) planes[c] = img.ch[bc + c].dev;
-        m.dev = (int32_t *)fuifgpu_dev_alloc(sizeof(int32_t) * (size_t)m.w * m.h);
-        rc = m.dev ? fuifgpu_fwd_match_frames(planes, nb, m.w, m.h, img.nb_frames, m.dev, nullptr) : FUIFGPU_E_HIP;
+        for (int c = 0; c < nb; c++) planes[c] = img.ch[bc + c].dev.i32();
+        rc = m.dev.alloc(sizeof(int32_t) * (size_t)m.w * m.h) ? fuifgpu_fwd_match_frames(planes, nb, m.w, m.h, img.nb_frames, m.dev.i32(), nullptr) : FUIFGPU_E_HIP;
     } else {
         m.data.assign((size_t)m.w * m.h, 0);
         fwd_match_frames_host(&img.ch[bc], nb, fh, m);
@@ -548,7 +599,7 @@ int fwd_quantize(Image &img, const Lossy &l, bool squeeze_option, bool colour_op
     std::vector<QuantChan> table;
     for (int i = img.nb_meta; i < n; i++) {
         Chan &c = img.ch[i];
-        table.push_back(QuantChan{c.dev, (int64_t)c.w * c.h, c.q, (int32_t)table.size(), 0, 0});
+        table.push_back(QuantChan{c.dev.i32(), (int64_t)c.w * c.h, c.q, (int32_t)table.size(), 0, 0});
     }
     std::vector<int32_t> minmax(2 * table.size());
     const int rc = fwd_quantize_channels_gpu(table.data(), (int)table.size(), minmax.data());
@@ -639,47 +690,34 @@ inline int props_and_guess(int32_t *p, const Chan &c, const std::vector<RefInfo>
     }
 }
 
-// ---- the writer's own tree learner: csrc/tree_learn.h (Learner, the recursive host learner of tree_mode 1, and learn_levelwise, the
-// level-wise one of tree_mode 2 whose statistics come from the kernels of maniac_encode.hip) --------------------------------------------
+// ---- one group (encoding/encoding.cpp:74-207 for a single-channel group), step by step ---------------------------------------------
+// The tree learner is csrc/tree_learn.h: Learner, the recursive host learner of tree_mode 1, and learn_levelwise, the level-wise one of
+// tree_mode 2 whose statistics come from the kernels of maniac_encode.hip.
+
+// what the groups of a call are coded with: the two chance transition tables, the options that bear on a group, and where the learner's
+// input comes from when it is not the channel's own samples
 struct GroupCoder {
+    std::vector<uint16_t> tables;   // the tree coder's table, then the pixel coder's
     const uint16_t *tree_table, *pixel_table;
     int max_properties, tree_mode, max_tree_nodes, split_bits;
-    int gpu_entropy = 0;            // the pixel loop of compressed groups runs in maniac_encode.hip
+    bool gpu_entropy = false;       // write_stream: the pixel loop of compressed groups runs in maniac_encode.hip
     EncScratch *scratch = nullptr;  // its device buffers, reused from group to group
-    int *gpu_rc = nullptr;          // first error of that path (there is no host route behind it)
     // device-only channels: the learner's samples of the picture's groups as k_learn_samples_jobs computed them, sample_job[channel] = job or -1
     const LearnSamples *samples = nullptr;
     const std::vector<int> *sample_job = nullptr;
     // tree_mode 2: the trees of the picture's groups as the level-wise learner left them (learn_trees_device), learned[channel]; a channel
     // that learns nothing has no entry
     const std::vector<std::vector<LearnNode>> *learned = nullptr;
+    explicit GroupCoder(const fuifgpu_encode_options &o)
+        : tables(16384), tree_table(tables.data()), pixel_table(tables.data() + 8192), max_properties(o.max_properties), tree_mode(o.tree_mode),
+          max_tree_nodes(o.max_tree_nodes), split_bits(o.split_bits > 0 ? o.split_bits : 0) {
+        build_chance_table(tables.data(), 0xFFFFFFFFu / 19, 2);
+        build_chance_table(tables.data() + 8192, 0x0d000000u, 6);
+    }
+    GroupCoder(const GroupCoder &) = delete;
 };
 
-// bytes of whole planes / channels the current encode call of this thread has moved (fuifgpu_encode_plane_traffic): every copy of
-// channel samples between host and device goes through these two
-thread_local uint64_t g_plane_h2d = 0, g_plane_d2h = 0;
-// what the tree learner of the current encode call has brought to the host (fuifgpu_encode_learn_traffic): sample rows and buckets
-// (tree_mode 1 on device-only channels), shortlists and record slices of the level statistics (tree_mode 2)
-thread_local uint64_t g_learn_sample_d2h = 0, g_learn_stat_d2h = 0;
-int plane_upload(int32_t *dev, const int32_t *host, size_t samples) {
-    g_plane_h2d += sizeof(int32_t) * samples;
-    return fuifgpu_dev_upload(dev, host, sizeof(int32_t) * samples);
-}
-int plane_download(int32_t *host, const int32_t *dev, size_t samples) {
-    g_plane_d2h += sizeof(int32_t) * samples;
-    return fuifgpu_dev_download(host, dev, sizeof(int32_t) * samples);
-}
-
-// a device copy of a channel's samples for the GPU pixel loop (kept until the stream is written)
-int ensure_dev(const Chan &c) {
-    if (c.dev || c.data.empty()) return FUIFGPU_OK;
-    c.dev = (int32_t *)fuifgpu_dev_alloc(sizeof(int32_t) * c.data.size());
-    if (!c.dev) return FUIFGPU_E_HIP;
-    if (c.hshift < 0) return fuifgpu_dev_upload(c.dev, c.data.data(), sizeof(int32_t) * c.data.size());   // a palette is a table, not a plane: not counted
-    return plane_upload(c.dev, c.data.data(), c.data.size());
-}
-
-// what the learner samples of a group (encode_group): every stride-th pixel, none for small groups or fixed trees
+// what the learner samples of a group: every stride-th pixel, none for small groups or fixed trees
 struct LearnPlan {
     size_t stride = 0, n_samples = 0;   // stride 0: no learned tree
     int max_depth = 14, min_leaf = 48;
@@ -703,15 +741,116 @@ LearnPlan plan_learner(const Chan &c, int tree_mode, int max_tree_nodes) {
     return lp;
 }
 
+// the group as the GPU pixel loop sees it: device copies of its plane and of its reference channels
+int build_enc_group(const Chan &c, const std::vector<RefInfo> &refs, int predictor, EncGroup &g) {
+    int rc = ensure_dev(c);
+    g = EncGroup{};
+    g.w = c.w; g.h = c.h; g.hshift = c.hshift; g.vshift = c.vshift;
+    g.minval = c.minval; g.maxval = c.maxval; g.zero = c.zero; g.predictor = predictor;
+    g.nrefs = (int)refs.size();
+    if (g.nrefs > kMaxRefs) rc = FUIFGPU_E_ARG;
+    for (int k = 0; k < g.nrefs && rc == FUIFGPU_OK; k++) {
+        const Chan &r = *refs[k].c;
+        rc = ensure_dev(r);
+        g.refs[k] = EncRef{r.dev.i32(), r.w, r.h, r.hshift, r.vshift};
+    }
+    g.plane = c.dev.i32();
+    return rc;
+}
+
+// a group in its compressed form as far as it is coded: header, zero chance, tree and (behind a pixel coder) the pixels; `state` is the
+// coder behind the last of them, not flushed
+struct CodedGroup {
+    Bytes bytes;
+    size_t header_len = 0;
+    bool trivial = false;           // minval == maxval: the header is all there is, no coder runs
+    RacEncState state{};
+};
+// ... and what the pixel coders need besides: the context model, the tree in the decoder's layout, the chances every leaf starts with
+struct GroupDraft {
+    CodedGroup coded;
+    std::vector<Range> ranges;
+    std::vector<RefInfo> refs;
+    int nprops = 0;
+    std::vector<EncNode> tree;
+    std::vector<uint16_t> leaves;   // n_leaves x CH_N
+    int n_leaves() const { return ((int)tree.size() + 1) / 2; }
+};
+
+// the group header (encoding.cpp:529-540): predictor and compress bit, the channel's range, its q unless the channel is all zero
+void group_header(Bytes &io, Chan &c, int predictor, bool compress) {
+    io.varint((size_t)((0 << 4) + (predictor << 1) + (compress ? 1 : 0)));
+    if (c.minval <= 0) io.varint((size_t)(1 - c.minval));
+    else { io.varint(0); io.varint((size_t)c.minval); }
+    io.varint((size_t)(c.maxval - c.minval));
+    if (!(c.minval == 0 && c.maxval == 0)) io.varint((size_t)c.q);
+    c.setzero();
+}
+
+// the group in its uncompressed form: the header and, unless the channel is trivial, every sample in a uniform code of its own coder.
+// A device-only channel comes to the host for this one loop
+int write_uncompressed(Bytes &io, Chan &c, int predictor) {
+    group_header(io, c, predictor, false);
+    if (c.minval == c.maxval) return FUIFGPU_OK;
+    int rc = FUIFGPU_OK;
+    std::vector<int32_t> fetched;
+    if (c.resident()) {
+        fetched.resize((size_t)c.w * c.h);
+        rc = plane_download(fetched.data(), c.dev.i32(), fetched.size());
+    }
+    RacEnc rac(io);
+    for (int32_t v : c.resident() ? fetched : c.data) uniform_write(rac, c.minval, c.maxval - c.minval, v);
+    rac.flush();
+    return rc;
+}
+
+// the tree of a group: learned from the host samples, from the rows k_learn_samples_jobs computed (device-only channels), or taken from
+// the level-wise learner's result (tree_mode 2); a single node in L.nodes where nothing is learned
+int group_tree(const Image &img, int ci, int predictor, const GroupCoder &gc, const GroupDraft &d, Learner &L) {
+    const Chan &c = img.ch[ci];
+    L.nodes.assign(1, Learner::LNode());
+    const LearnPlan lp = plan_learner(c, gc.tree_mode, gc.max_tree_nodes);
+    if (!lp.stride) return FUIFGPU_OK;
+    L.max_depth = lp.max_depth; L.min_leaf = lp.min_leaf;
+    L.nprops = d.nprops; L.scale = (double)lp.stride; L.max_nodes = gc.max_tree_nodes;
+    L.threshold_bits = (double)gc.split_bits;
+    if (gc.tree_mode == 2) {   // learned before the pictures' groups were written, all groups of the call in the same rounds
+        if (!gc.learned || (size_t)ci >= gc.learned->size() || (*gc.learned)[(size_t)ci].empty()) return FUIFGPU_E_HIP;   // (no host route behind it)
+        L.nodes = (*gc.learned)[(size_t)ci];
+        return FUIFGPU_OK;
+    }
+    if (c.resident()) {   // the same rows, in the same order, from the device
+        const int job = gc.samples && gc.sample_job ? (*gc.sample_job)[(size_t)ci] : -1;
+        if (job < 0) return FUIFGPU_E_HIP;
+        L.props.assign(gc.samples->props((size_t)job), gc.samples->props((size_t)job) + lp.n_samples * (size_t)d.nprops);
+        L.bucket.assign(gc.samples->bucket((size_t)job), gc.samples->bucket((size_t)job) + lp.n_samples);
+    } else {
+        std::vector<int32_t> props(d.nprops);
+        const size_t npix = (size_t)c.w * c.h;
+        for (size_t i = 0; i < npix; i += lp.stride) {
+            int y = (int)(i / c.w), x = (int)(i % c.w);
+            int guess = props_and_guess(props.data(), c, d.refs, x, y, predictor);
+            int diff = c.data[i] - guess;
+            L.props.insert(L.props.end(), props.begin(), props.end());
+            L.bucket.push_back((uint8_t)(diff == 0 ? 0 : ilog2u((uint32_t)iabs(diff)) + 1));
+        }
+    }
+    std::vector<int> idx(L.bucket.size());
+    for (size_t i = 0; i < idx.size(); i++) idx[i] = (int)i;
+    L.build(idx, 0, (int)idx.size(), 0, 0);
+    return FUIFGPU_OK;
+}
+
 // serialise a learned tree in pre-order (write side of compound.h:277-308) and build the
 // decoder-layout node array (children appended pairwise when the parent is parsed)
-void write_tree(RacEnc &rac, const Learner *L, std::vector<Range> ranges, const uint16_t *table, std::vector<TNode> &out) {
+void write_tree(RacEnc &rac, const Learner *L, std::vector<Range> ranges, const uint16_t *table, std::vector<EncNode> &out) {
     uint16_t ctx[3][CH_N];
     for (int k = 0; k < 3; k++) chance_init(ctx[k], 1024);
     const int nprops = (int)ranges.size();
-    out.assign(1, TNode());
+    static constexpr EncNode leaf_node{-1, 0, 0, 0};
+    out.assign(1, leaf_node);
     struct Rec {
-        RacEnc &rac; const Learner *L; std::vector<Range> &rg; const uint16_t *table; std::vector<TNode> &out; uint16_t (*ctx)[CH_N]; int nprops;
+        RacEnc &rac; const Learner *L; std::vector<Range> &rg; const uint16_t *table; std::vector<EncNode> &out; uint16_t (*ctx)[CH_N]; int nprops;
         void go(int lnode, int pos) {
             int p = (L && lnode >= 0) ? L->nodes[lnode].prop : -1;
             write_symbol2(rac, ctx[0], table, 0, nprops, p + 1);
@@ -723,7 +862,7 @@ void write_tree(RacEnc &rac, const Learner *L, std::vector<Range> ranges, const 
             out[pos].split = s;
             int child = (int)out.size();
             out[pos].child = child;
-            out.push_back(TNode()); out.push_back(TNode());
+            out.push_back(leaf_node); out.push_back(leaf_node);
             rg[p].lo = s + 1;
             go(L->nodes[lnode].gt, child);
             rg[p].lo = oldmin; rg[p].hi = s;
@@ -736,169 +875,371 @@ void write_tree(RacEnc &rac, const Learner *L, std::vector<Range> ranges, const 
     for (auto &n : out) if (n.prop < 0) n.leaf = leaf++;
 }
 
-// encoding/encoding.cpp:74-207 for one single-channel group; returns bytes after the group header
-// the group as the GPU pixel loop sees it: device copies of its plane and of its reference channels
-int build_enc_group(const Chan &c, const std::vector<RefInfo> &refs, int predictor, EncGroup &g) {
-    int rc = ensure_dev(c);
-    g = EncGroup{};
-    g.w = c.w; g.h = c.h; g.hshift = c.hshift; g.vshift = c.vshift;
-    g.minval = c.minval; g.maxval = c.maxval; g.zero = c.zero; g.predictor = predictor;
-    g.nrefs = (int)refs.size();
-    if (g.nrefs > kMaxRefs) rc = FUIFGPU_E_ARG;
-    for (int k = 0; k < g.nrefs && rc == FUIFGPU_OK; k++) {
-        const Chan &r = *refs[k].c;
-        rc = ensure_dev(r);
-        g.refs[k] = EncRef{r.dev, r.w, r.h, r.hshift, r.vshift};
-    }
-    g.plane = c.dev;
-    return rc;
-}
-
-// `defer`: (compressed groups only) stop behind the tree: the job gets the group for the GPU pixel loop and the coder's state, `io`
-// holds header + tree bytes, nothing is flushed -- the caller appends the job's bytes and flushes (batch encode)
-size_t encode_group(Bytes &io, Image &img, int ci, int predictor, bool compress, const GroupCoder &gc, size_t &header_pos, EncJob *defer = nullptr) {
+// the prefix of a group's compressed form: header, zero chance ("predictability" of a predictor-0 group), tree; d.leaves gets the chances
+// of every leaf and d.coded.state the coder behind the tree.  A trivial channel has its header only
+int group_prefix(Image &img, int ci, int predictor, const GroupCoder &gc, GroupDraft &d) {
     Chan &c = img.ch[ci];
-    io.varint((size_t)((0 << 4) + (predictor << 1) + (compress ? 1 : 0)));
-    if (c.minval <= 0) io.varint((size_t)(1 - c.minval));
-    else { io.varint(0); io.varint((size_t)c.minval); }
-    io.varint((size_t)(c.maxval - c.minval));
-    if (!(c.minval == 0 && c.maxval == 0)) io.varint((size_t)c.q);
-    c.setzero();
-    header_pos = io.b.size();
-    if (c.minval == c.maxval) return 0;  // trivial channel: no RAC stream
-
-    std::vector<Range> ranges; std::vector<RefInfo> refs;
-    const int nprops = init_properties(ranges, refs, img, ci, ci, gc.max_properties);
+    Bytes &io = d.coded.bytes;
+    group_header(io, c, predictor, true);
+    d.coded.header_len = io.b.size();
+    d.coded.trivial = c.minval == c.maxval;
+    if (d.coded.trivial) return FUIFGPU_OK;   // no RAC stream
+    d.nprops = init_properties(d.ranges, d.refs, img, ci, ci, gc.max_properties);
     int predictability = 2048;
-    if (predictor == 0 && compress) {
+    if (predictor == 0) {
         uint64_t zeroes = 0, pixels = (uint64_t)c.w * c.h;
-        if (c.zeros >= 0) zeroes = (uint64_t)c.zeros;
+        if (c.resident()) zeroes = (uint64_t)c.zeros;
         else for (int32_t v : c.data) zeroes += (v == 0);
         int rounded = (int)(zeroes * 128 / pixels);
         rounded = std::max(1, std::min(127, rounded));
         io.varint((size_t)rounded);
         predictability = rounded * 32;
     }
-    RacEnc rac(io);
-    if (!compress) {
-        std::vector<int32_t> fetched;   // a device-only channel comes to the host for this one loop
-        if (c.resident()) {
-            fetched.resize((size_t)c.w * c.h);
-            const int rc = plane_download(fetched.data(), c.dev, fetched.size());
-            if (rc != FUIFGPU_OK && gc.gpu_rc && *gc.gpu_rc == FUIFGPU_OK) *gc.gpu_rc = rc;
-        }
-        for (int32_t v : c.resident() ? fetched : c.data) uniform_write(rac, c.minval, c.maxval - c.minval, v);
-        rac.flush();
-        return io.b.size() - header_pos;
-    }
-    std::vector<int32_t> props(nprops);
     Learner L;
-    const Learner *use = nullptr;
-    const size_t npix = (size_t)c.w * c.h;
-    const LearnPlan lp = plan_learner(c, gc.tree_mode, gc.max_tree_nodes);
-    if (lp.stride) {
-        const size_t stride = lp.stride;
-        L.max_depth = lp.max_depth; L.min_leaf = lp.min_leaf;
-        L.nprops = nprops; L.scale = (double)stride; L.max_nodes = gc.max_tree_nodes;
-        L.threshold_bits = (double)gc.split_bits;
-        if (gc.tree_mode == 2) {   // learned before the pictures' groups were written, all groups of the call in the same rounds
-            if (gc.learned && (size_t)ci < gc.learned->size() && !(*gc.learned)[(size_t)ci].empty()) L.nodes = (*gc.learned)[(size_t)ci];
-            else { L.nodes.assign(1, Learner::LNode()); if (gc.gpu_rc && *gc.gpu_rc == FUIFGPU_OK) *gc.gpu_rc = FUIFGPU_E_HIP; }   // (no host route behind it)
-        } else if (c.resident()) {   // the same rows, in the same order, from the device
-            const int job = gc.samples && gc.sample_job ? (*gc.sample_job)[(size_t)ci] : -1;
-            if (job < 0) { if (gc.gpu_rc && *gc.gpu_rc == FUIFGPU_OK) *gc.gpu_rc = FUIFGPU_E_HIP; }
-            else {
-                L.props.assign(gc.samples->props((size_t)job), gc.samples->props((size_t)job) + lp.n_samples * (size_t)nprops);
-                L.bucket.assign(gc.samples->bucket((size_t)job), gc.samples->bucket((size_t)job) + lp.n_samples);
-            }
-        } else for (size_t i = 0; i < npix; i += stride) {
-            int y = (int)(i / c.w), x = (int)(i % c.w);
-            int guess = props_and_guess(props.data(), c, refs, x, y, predictor);
-            int d = c.data[i] - guess;
-            L.props.insert(L.props.end(), props.begin(), props.end());
-            L.bucket.push_back((uint8_t)(d == 0 ? 0 : ilog2u((uint32_t)iabs(d)) + 1));
-        }
-        if (gc.tree_mode != 2) {
-            std::vector<int> idx(L.bucket.size());
-            for (size_t i = 0; i < idx.size(); i++) idx[i] = (int)i;
-            L.nodes.assign(1, Learner::LNode());
-            L.build(idx, 0, (int)idx.size(), 0, 0);
-        }
-        if (L.nodes.size() > 1) use = &L;
-    }
-    std::vector<TNode> tree;
-    write_tree(rac, use, ranges, gc.tree_table, tree);
-    const int nleaves = ((int)tree.size() + 1) / 2;
-    std::vector<uint16_t> leaves((size_t)nleaves * CH_N);
-    chance_init(leaves.data(), predictability);
-    for (int l = 1; l < nleaves; l++) memcpy(&leaves[(size_t)l * CH_N], leaves.data(), sizeof(uint16_t) * CH_N);
-    if (defer) {
-        const int rc = build_enc_group(c, refs, predictor, defer->g);
-        defer->tree.resize(tree.size());
-        for (size_t k = 0; k < tree.size(); k++) defer->tree[k] = EncNode{tree[k].prop, tree[k].split, tree[k].child, tree[k].leaf};
-        defer->n_leaves = nleaves;
-        memcpy(defer->leaf_init, leaves.data(), sizeof(uint16_t) * CH_N);
-        defer->state = RacEncState{rac.range, rac.low, rac.delayed, rac.pending};
-        if (rc != FUIFGPU_OK && gc.gpu_rc && *gc.gpu_rc == FUIFGPU_OK) *gc.gpu_rc = rc;
-        return io.b.size() - header_pos;
-    }
-    if (gc.gpu_entropy) {
-        // every sample is known: the context model of all pixels runs in parallel, one wavefront then codes them in order into
-        // THIS range coder (its state goes to the device and comes back; the tree above is already in it)
-        EncGroup g{};
-        int rc = build_enc_group(c, refs, predictor, g);
-        if (rc == FUIFGPU_OK) {
-            std::vector<EncNode> nodes(tree.size());
-            for (size_t k = 0; k < tree.size(); k++) nodes[k] = EncNode{tree[k].prop, tree[k].split, tree[k].child, tree[k].leaf};
-            RacEncState st{rac.range, rac.low, rac.delayed, rac.pending};
-            rc = maniac_encode_group_gpu(g, nodes.data(), (int)nodes.size(), nleaves, leaves.data(), gc.pixel_table, &st, io.b, *gc.scratch);
-            rac.range = st.range; rac.low = st.low; rac.delayed = st.delayed; rac.pending = st.pending;
-        }
-        if (rc != FUIFGPU_OK && gc.gpu_rc && *gc.gpu_rc == FUIFGPU_OK) *gc.gpu_rc = rc;
-    } else if (tree.size() == 1 && predictor == 0 && c.zero == 0) {
-        for (int32_t v : c.data) write_symbol(rac, leaves.data(), gc.pixel_table, c.minval, c.maxval, v);  // fast track
+    const int rc = group_tree(img, ci, predictor, gc, d, L);
+    if (rc != FUIFGPU_OK) return rc;
+    RacEnc rac(io);
+    write_tree(rac, L.nodes.size() > 1 ? &L : nullptr, d.ranges, gc.tree_table, d.tree);
+    d.leaves.resize((size_t)d.n_leaves() * CH_N);
+    chance_init(d.leaves.data(), predictability);
+    for (int l = 1; l < d.n_leaves(); l++) memcpy(&d.leaves[(size_t)l * CH_N], d.leaves.data(), sizeof(uint16_t) * CH_N);
+    d.coded.state = rac.st;
+    return FUIFGPU_OK;
+}
+
+// the pixels of a group behind its prefix, three ways.  1: the host loop
+void code_pixels_host(const Chan &c, int predictor, const GroupCoder &gc, GroupDraft &d) {
+    RacEnc rac(d.coded.bytes, d.coded.state);
+    const std::vector<EncNode> &tree = d.tree;
+    if (tree.size() == 1 && predictor == 0 && c.zero == 0) {
+        for (int32_t v : c.data) write_symbol(rac, d.leaves.data(), gc.pixel_table, c.minval, c.maxval, v);  // fast track
     } else {
+        std::vector<int32_t> props(d.nprops);
         for (int y = 0; y < c.h; y++)
             for (int x = 0; x < c.w; x++) {
-                int guess = props_and_guess(props.data(), c, refs, x, y, predictor);
+                int guess = props_and_guess(props.data(), c, d.refs, x, y, predictor);
                 int mn = c.minval - guess, mx = c.maxval - guess;
                 if (mn == mx) continue;
                 int pos = 0;
                 while (tree[pos].prop >= 0) pos = (props[tree[pos].prop] > tree[pos].split) ? tree[pos].child : tree[pos].child + 1;
-                write_symbol(rac, &leaves[(size_t)tree[pos].leaf * CH_N], gc.pixel_table, mn, mx, c.data[(size_t)y * c.w + x] - guess);
+                write_symbol(rac, &d.leaves[(size_t)tree[pos].leaf * CH_N], gc.pixel_table, mn, mx, c.data[(size_t)y * c.w + x] - guess);
             }
     }
-    rac.flush();
-    return io.b.size() - header_pos;
+    d.coded.state = rac.st;
+}
+// 2: every sample is known, so the context model of all pixels runs in parallel and one wavefront then codes them in order into THIS
+// range coder (its state goes to the device and comes back; the tree is already in it)
+int code_pixels_gpu(const Chan &c, int predictor, const GroupCoder &gc, GroupDraft &d) {
+    EncGroup g{};
+    const int rc = build_enc_group(c, d.refs, predictor, g);
+    if (rc != FUIFGPU_OK) return rc;
+    return maniac_encode_group_gpu(g, d.tree.data(), (int)d.tree.size(), d.n_leaves(), d.leaves.data(), gc.pixel_table, &d.coded.state, d.coded.bytes.b, *gc.scratch);
+}
+// 3: a job of maniac_encode_jobs_gpu, which codes the groups of a whole batch in one launch pair (the caller takes job.body and job.state back)
+int make_enc_job(const Chan &c, int predictor, GroupDraft &d, EncJob &job) {
+    const int rc = build_enc_group(c, d.refs, predictor, job.g);
+    job.n_leaves = d.n_leaves();
+    job.tree = std::move(d.tree);
+    memcpy(job.leaf_init, d.leaves.data(), sizeof(uint16_t) * CH_N);
+    job.state = d.coded.state;
+    return rc;
 }
 
-}  // namespace
-}  // namespace fuifgpu
+// a stream as it is assembled: the fixed header fields, everything behind them, and what is noted on the way
+struct StreamOut {
+    Bytes head, io;
+    int responsive[5] = {-1, -1, -1, -1, -1};
+    std::vector<GroupEntry> group_at;  // group starts relative to `io` (made absolute by finish_stream)
+    StaleTail stale;
+};
 
-using namespace fuifgpu;
-
-namespace fuifgpu {
-namespace {
-int write_stream(Image &img, int nch, int bit_depth, bool squeezed, const fuifgpu_encode_options &o, uint8_t **blob_out, size_t *size_out,
-                 bool dct_style = false);
+// The end of every group, for both stream writers: flush the coder behind the last symbol; keep the compressed form if it is smaller than
+// the samples' raw bits, else (encoding.cpp:545-551) roll back and store the group uncompressed -- a trivial channel always: the reference
+// re-encodes it "uncompressed" too (compress bit = 0); tell StaleTail what was abandoned; note where the group starts and the responsive
+// offset it ends
+int settle_group(StreamOut &out, Image &img, int i, int predictor, CodedGroup &cg) {
+    Chan &c = img.ch[i];
+    Bytes &io = out.io;
+    const size_t before = io.b.size();
+    out.group_at.push_back(GroupEntry{(uint32_t)before, i});
+    if (!cg.trivial) RacEnc(cg.bytes, cg.state).flush();
+    const size_t body = cg.bytes.b.size() - cg.header_len;
+    float bits = body * 8.0f, pixels = (float)c.w * c.h, ubits = 0.0f;
+    if (c.maxval > c.minval) ubits = pixels * (ilog2u((uint32_t)(c.maxval - c.minval)) + 1) + 16;
+    int rc = FUIFGPU_OK;
+    if (bits >= ubits) {
+        if (img.stale_tail) out.stale.abandoned(before, cg.bytes.b.data(), cg.bytes.b.size());
+        rc = write_uncompressed(io, c, predictor);
+    } else io.b.insert(io.b.end(), cg.bytes.b.begin(), cg.bytes.b.end());
+    for (int s = 0; s < 5; s++) if (img.downscales[s] == i) out.responsive[s] = (int)io.b.size();
+    return rc;
 }
-}  // namespace fuifgpu
 
-static int squeeze_quantize_and_fetch(fuifgpu::Image &img, const fuifgpu_encode_options &o, const fuifgpu::Lossy &lossy, bool colour_option, bool on_gpu,
-                                      bool keep_resident, bool &squeezed, int rc);
-static int encode_images_common(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
-                                const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette, uint8_t **blobs_out, size_t *sizes_out,
-                                bool device_input, const fuifgpu_animation_options *anim_options);
+// ---- what write_stream and write_streams_batch share besides -------------------------------------------------------------------------
+// fuif_prepare_encode (encoding.cpp:737-743): every channel's range from its samples.  Host channels are scanned here; device-only ones
+// (of all pictures) go through ONE k_channel_stats launch, which also counts their zeros for the "predictability" byte
+int channel_ranges(Image *imgs, size_t n_images) {
+    std::vector<Chan *> who;
+    for (size_t m = 0; m < n_images; m++)
+        for (Chan &c : imgs[m].ch) {
+            if (c.resident()) who.push_back(&c);
+            else c.minmax();
+        }
+    return device_ranges(who);
+}
+int group_predictor(const Image &img, int i) {  // fuif.cpp:580-588
+    if (i < img.nb_meta) return 3;   // "left" for the palettes
+    if (!img.squeezed && !img.dct_style) return 2;
+    return i < img.nb_meta + img.nb_channels ? 2 : 0;
+}
+void responsive_downscales(Image &img) {
+    recompute_downscales(img);
+    if (!img.squeezed && !img.dct_style) for (int s = 0; s < 6; s++) img.downscales[s] = (int)img.ch.size() - 1;
+}
+// what to sample of channel i's group on the device, if the group learns a tree at all (else lp.stride stays 0)
+int learn_job(Image &img, int i, const GroupCoder &gc, LearnPlan &lp, LearnJob &job) {
+    Chan &c = img.ch[i];
+    if (!c.w || !c.h || c.minval == c.maxval) return FUIFGPU_OK;
+    lp = plan_learner(c, gc.tree_mode, gc.max_tree_nodes);
+    if (!lp.stride) return FUIFGPU_OK;
+    c.setzero();
+    std::vector<Range> ranges; std::vector<RefInfo> refs;
+    job.nprops = init_properties(ranges, refs, img, i, i, gc.max_properties);
+    job.n_samples = (int64_t)lp.n_samples; job.stride = (int64_t)lp.stride;
+    return build_enc_group(c, refs, group_predictor(img, i), job.g);
+}
+// the learner's samples of a picture's device-only groups (what group_tree's sampling loop computes for host channels), in one launch:
+// sample_job[channel] = its job in `out`, -1 for channels that learn nothing or have their samples on the host
+int learn_samples_device(Image &img, const GroupCoder &gc, LearnSamples &out, std::vector<int> &sample_job) {
+    std::vector<LearnJob> jobs;
+    sample_job.assign(img.ch.size(), -1);
+    for (int i = 0; i < (int)img.ch.size(); i++) {
+        LearnPlan lp;
+        LearnJob job;
+        const int rc = img.ch[i].resident() ? learn_job(img, i, gc, lp, job) : FUIFGPU_OK;
+        if (rc != FUIFGPU_OK) return rc;
+        if (!lp.stride) continue;
+        sample_job[(size_t)i] = (int)jobs.size();
+        jobs.push_back(job);
+    }
+    const int rc = learn_samples_jobs_gpu(jobs, out);
+    g_learn_sample_d2h += out.raw.size() * sizeof(int32_t);
+    return rc;
+}
+// tree_mode 2: the trees of every learning group of every picture of the call.  Host-resident channels go to the device here, one phase
+// earlier than for the GPU pixel loop (the same copies); the samples are computed there and stay there.  learned[m][channel]
+int learn_trees_device(std::vector<Image> &imgs, const GroupCoder &gc, std::vector<std::vector<std::vector<LearnNode>>> &learned) {
+    std::vector<LearnTreeJob> jobs;
+    std::vector<std::pair<size_t, int>> where;
+    learned.assign(imgs.size(), std::vector<std::vector<LearnNode>>());
+    for (size_t m = 0; m < imgs.size(); m++) {
+        Image &img = imgs[m];
+        learned[m].resize(img.ch.size());
+        for (int i = 0; i < (int)img.ch.size(); i++) {
+            LearnPlan lp;
+            LearnTreeJob job;
+            const int rc = learn_job(img, i, gc, lp, job.sample);
+            if (rc != FUIFGPU_OK) return rc;
+            if (!lp.stride) continue;
+            job.prm.max_nodes = gc.max_tree_nodes; job.prm.max_depth = lp.max_depth; job.prm.min_leaf = lp.min_leaf;
+            job.prm.threshold_bits = (double)gc.split_bits; job.prm.scale = (double)lp.stride;
+            where.push_back(std::make_pair(m, i));
+            jobs.push_back(std::move(job));
+        }
+    }
+    uint64_t stat_bytes = 0;
+    const int rc = learn_trees_gpu(jobs, &stat_bytes);
+    g_learn_stat_d2h += stat_bytes;
+    for (size_t k = 0; k < jobs.size() && rc == FUIFGPU_OK; k++) learned[where[k].first][(size_t)where[k].second].swap(jobs[k].nodes);
+    return rc;
+}
+// encoding/encoding.cpp:455-470: the fixed header fields into `head`, the transform list into `io`
+void begin_stream(const Image &img, int nch, int bit_depth, const fuifgpu_encode_options &o, StreamOut &out) {
+    Bytes &head = out.head;
+    for (const char *m = img.nb_frames > 1 ? "FUAF" : "FUIF"; *m; m++) head.put(*m);
+    head.varint((size_t)(nch + '0'));
+    head.varint((size_t)(bit_depth + '&'));
+    head.varint((size_t)(img.w - 1));
+    head.varint((size_t)(img.h - 1));
+    if (img.nb_frames > 1) {   // encoding.cpp:467-473: no per-frame numerators, no loop count
+        head.varint((size_t)(img.nb_frames - 2));
+        head.varint((size_t)(img.den - 1));
+        head.varint(0);
+        head.varint(0);
+    }
+    head.varint(0);  // colormodel
+    head.varint((size_t)o.max_properties);
+    out.io.varint(img.transforms.size());
+    for (auto &t : img.transforms) {
+        out.io.varint((size_t)((t.params.size() << 4) + t.id));
+        for (int v : t.params) out.io.varint((size_t)v);
+    }
+}
+// encoding.cpp:552-573: the responsive offsets behind the header, the groups, what the reference's buffer holds behind them
+// (Image::stale_tail), the optional index trailer -> one malloc'ed blob
+int finish_stream(StreamOut &out, bool emit_index, uint8_t **blob_out, size_t *size_out) {
+    Bytes &head = out.head;
+    const Bytes &io = out.io;
+    int rel = 0;
+    for (int s = 0; s < 5; s++) {
+        if (out.responsive[s] < 0) out.responsive[s] = (int)io.b.size();
+        head.varint((size_t)(out.responsive[s] - rel));
+        rel = out.responsive[s];
+    }
+    const std::vector<uint8_t> stale = out.stale.behind(io.b.size());
+    std::vector<uint8_t> trailer;
+    if (emit_index && !out.group_at.empty()) {
+        // the transform list sits between the header and the first group: offsets become absolute here
+        for (GroupEntry &g : out.group_at) g.start += (uint32_t)head.b.size();
+        build_index_trailer(out.group_at, trailer);
+    }
+    const size_t total = head.b.size() + io.b.size() + stale.size() + trailer.size();
+    uint8_t *blob = (uint8_t *)malloc(total ? total : 1);
+    if (!blob) return FUIFGPU_E_NOMEM;
+    memcpy(blob, head.b.data(), head.b.size());
+    memcpy(blob + head.b.size(), io.b.data(), io.b.size());
+    if (!stale.empty()) memcpy(blob + head.b.size() + io.b.size(), stale.data(), stale.size());
+    if (!trailer.empty()) memcpy(blob + head.b.size() + io.b.size() + stale.size(), trailer.data(), trailer.size());
+    *blob_out = blob;
+    *size_out = total;
+    return FUIFGPU_OK;
+}
+
+// ---- one picture: group by group, the pixel loops on the host or (gpu_entropy) one launch pair per group -----------------------------
+// encoding/encoding.cpp:455-573.  The picture is taken over: its device copies and the coder's buffers live as long as this call.
+// There is no host route behind the GPU pixel loop: the caller asked for it
+int write_stream(Image img, int nch, int bit_depth, const fuifgpu_encode_options &o, uint8_t **blob_out, size_t *size_out) {
+    if (o.tree_mode == 2)   // (fuifgpu_encode_channels; every other entry point takes tree_mode 2 to the batch writer)
+        return fail_with_message(FUIFGPU_E_UNSUPPORTED, "tree_mode 2 (trees learned with GPU statistics) is not offered for channels in a transform domain: use tree_mode 1");
+    EncScratch enc_scratch;
+    int rc = channel_ranges(&img, 1);
+    if (rc != FUIFGPU_OK) return rc;
+    responsive_downscales(img);
+    GroupCoder gc(o);
+    gc.gpu_entropy = o.gpu_entropy != 0; gc.scratch = &enc_scratch;
+    StreamOut out;
+    begin_stream(img, nch, bit_depth, o, out);
+    for (int i = 0; i < (int)img.ch.size(); i++) {
+        Chan &c = img.ch[i];
+        if (!c.w || !c.h) continue;
+        const int predictor = group_predictor(img, i);
+        GroupDraft d;
+        rc = group_prefix(img, i, predictor, gc, d);
+        if (rc == FUIFGPU_OK && !d.coded.trivial) {
+            if (gc.gpu_entropy) rc = code_pixels_gpu(c, predictor, gc, d);
+            else code_pixels_host(c, predictor, gc, d);
+        }
+        if (rc == FUIFGPU_OK) rc = settle_group(out, img, i, predictor, d.coded);
+        if (rc != FUIFGPU_OK) return rc;
+    }
+    return finish_stream(out, o.emit_index != 0, blob_out, size_out);
+}
+
+// ---- a batch of pictures: every compressed group's pixel loop in ONE launch pair ------------------------------------------------
+// Phase 1 (host, per picture): per group the prefix (header + zero chance + learned tree) into its own byte buffer, the coder's
+// state behind the tree, and a job.  Phase 2 (GPU): maniac_encode_jobs_gpu -- the context model of every pixel of every group in
+// one launch, then one wavefront per group.  Phase 3 (host, per picture): header fields, settle_group for every group, group index.
+// Same bytes as write_stream picture by picture.
+// Device-only channels (fuifgpu_encode_images_device) take the same three phases: their ranges and zero counts come from one
+// statistics launch, the learner's samples of a picture from one k_learn_samples_jobs launch, and build_enc_group hands their
+// buffers to the coder as they are; only a group that is rolled back comes to the host.
+struct PendingGroup {
+    int channel = 0, predictor = 0, job = -1;   // job -1: a trivial channel (no coder)
+    CodedGroup coded;
+};
+int write_streams_batch(std::vector<Image> &imgs, int nch, int bit_depth, const fuifgpu_encode_options &o, uint8_t **blobs_out, size_t *sizes_out) {
+    GroupCoder gc(o);
+    if (o.tree_mode == 2) {   // no silent host route: without a device the call fails whatever the pictures hold
+        int n_devices = 0;
+        const int rc = fuifgpu_device_count(&n_devices);
+        if (rc != FUIFGPU_OK) return rc;
+    }
+    int rc = channel_ranges(imgs.data(), imgs.size());
+    if (rc != FUIFGPU_OK) return rc;
+    std::vector<std::vector<std::vector<LearnNode>>> learned;
+    if (gc.tree_mode == 2) {
+        rc = learn_trees_device(imgs, gc, learned);
+        if (rc != FUIFGPU_OK) return rc;
+    }
+    std::vector<EncJob> jobs;
+    std::vector<std::vector<PendingGroup>> pending(imgs.size());
+    for (size_t m = 0; m < imgs.size(); m++) {
+        Image &img = imgs[m];
+        responsive_downscales(img);
+        LearnSamples samples;
+        std::vector<int> sample_job;
+        rc = gc.tree_mode == 2 ? FUIFGPU_OK : learn_samples_device(img, gc, samples, sample_job);
+        if (rc != FUIFGPU_OK) return rc;
+        gc.samples = &samples; gc.sample_job = &sample_job;
+        gc.learned = gc.tree_mode == 2 ? &learned[m] : nullptr;
+        for (int i = 0; i < (int)img.ch.size(); i++) {
+            Chan &c = img.ch[i];
+            if (!c.w || !c.h) continue;
+            PendingGroup pg;
+            pg.channel = i;
+            pg.predictor = group_predictor(img, i);
+            GroupDraft d;
+            rc = group_prefix(img, i, pg.predictor, gc, d);
+            if (rc == FUIFGPU_OK && !d.coded.trivial) {
+                EncJob job;
+                rc = make_enc_job(c, pg.predictor, d, job);
+                pg.job = (int)jobs.size();
+                jobs.push_back(std::move(job));
+            }
+            if (rc != FUIFGPU_OK) return rc;
+            pg.coded = std::move(d.coded);
+            pending[m].push_back(std::move(pg));
+        }
+        gc.samples = nullptr; gc.sample_job = nullptr; gc.learned = nullptr;
+    }
+    rc = maniac_encode_jobs_gpu(jobs, gc.pixel_table);
+    if (rc != FUIFGPU_OK) return rc;
+    for (size_t m = 0; m < imgs.size(); m++) {
+        StreamOut out;
+        begin_stream(imgs[m], nch, bit_depth, o, out);
+        for (PendingGroup &pg : pending[m]) {
+            if (pg.job >= 0) {
+                const EncJob &job = jobs[(size_t)pg.job];
+                pg.coded.bytes.b.insert(pg.coded.bytes.b.end(), job.body.begin(), job.body.end());
+                pg.coded.state = job.state;
+            }
+            rc = settle_group(out, imgs[m], pg.channel, pg.predictor, pg.coded);   // (a device-only channel that is rolled back comes to the host here)
+            if (rc != FUIFGPU_OK) return rc;
+        }
+        rc = finish_stream(out, o.emit_index != 0, &blobs_out[m], &sizes_out[m]);
+        if (rc != FUIFGPU_OK) return rc;
+    }
+    return FUIFGPU_OK;
+}
+
+// ---- the input routes: planes -> transformed Image ------------------------------------------------------------------------------------
+// the end of every input route (fuif.cpp:450-503): default Squeeze, Quantize, and the transformed channels back from the GPU unless they
+// stay there (keep_resident).  The channels may differ in geometry from the start (.yuv input).  colour_option: `colorspace != 0`, components
+// 1 and 2 take the chroma table.  rc: what the steps before have come to -- after a failure only the device buffers are released
+int squeeze_quantize_and_fetch(Image &img, const fuifgpu_encode_options &o, const Lossy &lossy, bool colour_option, bool on_gpu, bool keep_resident, int rc) {
+    if (rc == FUIFGPU_OK && o.squeeze) rc = default_squeeze(img, on_gpu);
+    std::vector<char> all_zero(img.ch.size(), 0);   // gpu_forward + lossy: channels whose quotients are all 0 stay on the device
+    if (rc == FUIFGPU_OK && lossy.active) rc = fwd_quantize(img, lossy, o.squeeze != 0, colour_option, on_gpu, all_zero);   // fuif.cpp:459-503
+    if (on_gpu && (!keep_resident || rc != FUIFGPU_OK)) {
+        for (size_t k = 0; k < img.ch.size(); k++) {
+            Chan &ch = img.ch[k];
+            if (rc == FUIFGPU_OK && ch.dev) {
+                ch.data.assign((size_t)ch.w * ch.h, 0);
+                if (!ch.data.empty() && !all_zero[k]) rc = plane_download(ch.data.data(), ch.dev.i32(), ch.data.size());
+            }
+            ch.dev.reset();
+        }
+    }
+    return rc;   // (no host route behind a failed GPU transform: the caller asked for the GPU)
+}
 
 // planes -> Image with the CLI's default forward transforms applied (fuif.cpp:380-455) and, with a quality, its Quantize (fuif.cpp:459-503),
 // on the host or on the GPU.  device_input: `planes` is device memory -- the forward transforms run on working copies there (gpu_forward is
 // implied) and the transformed channels STAY there, device-only (Chan::resident), for write_streams_batch
 // An animation (anim.nb_frames > 1): `planes` holds the frames one after the other, each nch planes of w x frame_h; channel c of the strip
 // is plane c of every frame, one above the other (fuif.cpp:319-327)
-static int build_transformed_image(const int32_t *planes, int w, int frame_h, int nch, int bit_depth, const fuifgpu_encode_options &o,
-                                   const fuifgpu::Lossy &lossy, fuifgpu::PaletteOpts pal, const fuifgpu::AnimOpts &anim, fuifgpu::Image &img, bool &squeezed,
-                                   bool device_input = false) {
-    using namespace fuifgpu;
+int build_transformed_image(const int32_t *planes, int w, int frame_h, int nch, int bit_depth, const fuifgpu_encode_options &o, const Lossy &lossy,
+                            PaletteOpts pal, const AnimOpts &anim, Image &img, bool device_input = false) {
     if (lossy.quality < 100.f && pal.colors > 0) pal = PaletteOpts();   // fuif.cpp:345-350: `quality` alone is read, and only -K > 0 clears the other two
     const int h = frame_h * anim.nb_frames;
     const size_t frame_samples = (size_t)w * frame_h;
@@ -921,19 +1262,18 @@ static int build_transformed_image(const int32_t *planes, int w, int frame_h, in
         // the planes go to the GPU once, every forward transform runs there, the transformed channels come back for the entropy coder
         for (int c = 0; c < nch && rc == FUIFGPU_OK; c++) {
             Chan &ch = img.ch[c];
-            ch.dev = (int32_t *)fuifgpu_dev_alloc(sizeof(int32_t) * (size_t)w * h);
-            if (!ch.dev) rc = FUIFGPU_E_HIP;
+            if (!ch.dev.alloc(sizeof(int32_t) * (size_t)w * h)) rc = FUIFGPU_E_HIP;
             else if (device_input)   // the caller's planes are never written
                 for (int f = 0; f < anim.nb_frames && rc == FUIFGPU_OK; f++)
-                    rc = dev_copy(ch.dev + (size_t)f * frame_samples, planes + ((size_t)f * nch + c) * frame_samples, sizeof(int32_t) * frame_samples);
-            else rc = plane_upload(ch.dev, ch.data.data(), (size_t)w * h);
+                    rc = dev_copy(ch.dev.i32() + (size_t)f * frame_samples, planes + ((size_t)f * nch + c) * frame_samples, sizeof(int32_t) * frame_samples);
+            else rc = plane_upload(ch.dev.i32(), ch.data.data(), (size_t)w * h);
             ch.data.clear();
         }
     }
     if (rc == FUIFGPU_OK && pal.pre > 0.f && o.ycocg) rc = compact_channels(img, pal.pre, true, on_gpu);   // fuif.cpp:374-388
     if (rc == FUIFGPU_OK && o.ycocg && nch >= 3) {
         const int m = img.nb_meta;
-        if (on_gpu) rc = fuifgpu_fwd_ycocg(img.ch[m].dev, img.ch[m + 1].dev, img.ch[m + 2].dev, w, h, nullptr);
+        if (on_gpu) rc = fuifgpu_fwd_ycocg(img.ch[m].dev.i32(), img.ch[m + 1].dev.i32(), img.ch[m + 2].dev.i32(), w, h, nullptr);
         else fwd_ycocg(img);
         img.transforms.push_back({TR_YCOCG, {}});
     }
@@ -943,57 +1283,35 @@ static int build_transformed_image(const int32_t *planes, int w, int frame_h, in
     }
     if (rc == FUIFGPU_OK && pal.post > 0.f) rc = compact_channels(img, pal.post, false, on_gpu);   // fuif.cpp:418-430
     if (rc == FUIFGPU_OK && anim.nb_frames > 1 && anim.match) rc = fwd_match_frames(img, on_gpu);   // fuif.cpp:440-448
-    return squeeze_quantize_and_fetch(img, o, lossy, o.ycocg != 0, on_gpu, device_input, squeezed, rc);
-}
-// the end of every input route (fuif.cpp:450-503): default Squeeze, Quantize, and the transformed channels back from the GPU unless they
-// stay there (keep_resident).  The channels may differ in geometry from the start (.yuv input).  colour_option: `colorspace != 0`, components
-// 1 and 2 take the chroma table.  rc: what the steps before have come to -- after a failure only the device buffers are released
-static int squeeze_quantize_and_fetch(fuifgpu::Image &img, const fuifgpu_encode_options &o, const fuifgpu::Lossy &lossy, bool colour_option, bool on_gpu,
-                                      bool keep_resident, bool &squeezed, int rc) {
-    using namespace fuifgpu;
-    squeezed = false;
-    if (rc == FUIFGPU_OK && o.squeeze && (int64_t)img.ch[0].w * img.ch[0].h > 20) {  // fuif.cpp:453: channel[0] -- the match channel or a palette, once there is one
-        std::vector<int> params = default_squeeze_params(img);
-        rc = fwd_squeeze(img, params, on_gpu);
-        img.transforms.push_back({TR_SQUEEZE, {}});  // empty parameter list = "default" in the stream
-        squeezed = true;
-    }
-    std::vector<char> all_zero(img.ch.size(), 0);   // gpu_forward + lossy: channels whose quotients are all 0 stay on the device
-    if (rc == FUIFGPU_OK && lossy.active) rc = fwd_quantize(img, lossy, o.squeeze != 0, colour_option, on_gpu, all_zero);   // fuif.cpp:459-503
-    if (on_gpu && (!keep_resident || rc != FUIFGPU_OK)) {
-        for (size_t k = 0; k < img.ch.size(); k++) {
-            Chan &ch = img.ch[k];
-            if (rc == FUIFGPU_OK && ch.dev) {
-                ch.data.assign((size_t)ch.w * ch.h, 0);
-                if (!ch.data.empty() && !all_zero[k]) rc = plane_download(ch.data.data(), ch.dev, ch.data.size());
-            }
-            if (ch.dev) fuifgpu_dev_free(ch.dev);
-            ch.dev = nullptr;
-        }
-    }
-    return rc;   // (no host route behind a failed GPU transform: the caller asked for the GPU)
+    return squeeze_quantize_and_fetch(img, o, lossy, o.ycocg != 0, on_gpu, device_input, rc);
 }
 
-extern "C" {
-
-void fuifgpu_free_blob(uint8_t *p) { free(p); }
-
-// fuifgpu_encode_options is versioned by its first field (include/fuifgpu.h): copy what the caller's header knows, zero the rest
-static bool read_encode_options(const fuifgpu_encode_options *opt, fuifgpu_encode_options &o, int gpu_entropy_default) {
+// ---- what every entry point starts with -----------------------------------------------------------------------------------------------
+// fuifgpu_encode_options is versioned by its first field (include/fuifgpu.h): copy what the caller's header knows, zero the rest.  Then
+// the entry point's other argument checks (`others`, in the place they have always had: a refused call reports the same code and message),
+// max_properties, the clamp of max_tree_nodes, and the traffic counters of the call start at zero
+template <class OtherChecks>
+int begin_encode_call(const fuifgpu_encode_options *opt, int gpu_entropy_default, fuifgpu_encode_options &o, OtherChecks others) {
     memset(&o, 0, sizeof(o));
     if (!opt) {
         o.ycocg = 1; o.squeeze = 1; o.max_properties = 12; o.tree_mode = 1; o.max_tree_nodes = 4095; o.gpu_entropy = gpu_entropy_default;
     } else {
         const uint32_t sz = opt->struct_size;
-        if (sz < 2 * sizeof(uint32_t) || (sz & 3u)) return false;
+        if (sz < 2 * sizeof(uint32_t) || (sz & 3u)) return FUIFGPU_E_ARG;
         memcpy(&o, opt, sz < sizeof(o) ? sz : sizeof(o));
     }
     o.struct_size = (uint32_t)sizeof(o);
-    return true;
+    if (const int rc = others()) return rc;
+    if (o.max_properties < 0 || o.max_properties > 2 * kMaxRefs) return FUIFGPU_E_ARG;
+    if (o.max_tree_nodes < 1) o.max_tree_nodes = 4095;
+    if (o.max_tree_nodes > kMaxNodes) o.max_tree_nodes = kMaxNodes;
+    g_plane_h2d = g_plane_d2h = 0;
+    g_learn_sample_d2h = g_learn_stat_d2h = 0;
+    return FUIFGPU_OK;
 }
 
 // fuifgpu_lossy_options is versioned like fuifgpu_encode_options; NULL = lossless.  A struct that ends before chroma_quality: same as quality
-static bool read_lossy_options(const fuifgpu_lossy_options *lossy, Lossy &l) {
+bool read_lossy_options(const fuifgpu_lossy_options *lossy, Lossy &l) {
     l = Lossy();
     if (!lossy) return true;
     const uint32_t sz = lossy->struct_size;
@@ -1002,7 +1320,7 @@ static bool read_lossy_options(const fuifgpu_lossy_options *lossy, Lossy &l) {
 }
 
 // fuifgpu_palette_options is versioned like the other two; NULL, or fields the caller's struct ends before, = 0 = off
-static bool read_palette_options(const fuifgpu_palette_options *palette, int nch, PaletteOpts &p) {
+bool read_palette_options(const fuifgpu_palette_options *palette, int nch, PaletteOpts &p) {
     p = PaletteOpts();
     if (!palette) return true;
     const uint32_t sz = palette->struct_size;
@@ -1021,7 +1339,7 @@ static bool read_palette_options(const fuifgpu_palette_options *palette, int nch
 
 // fuifgpu_animation_options: NULL = one frame; the strip must fit the format (h an int, a channel at most 2^31-1 samples) and the offset
 // code 2*fh*fh + 1 an int
-static int read_animation_options(const fuifgpu_animation_options *anim, int w, int frame_h, AnimOpts &a) {
+int read_animation_options(const fuifgpu_animation_options *anim, int w, int frame_h, AnimOpts &a) {
     a = AnimOpts();
     if (anim) {
         if (anim->struct_size < sizeof(fuifgpu_animation_options) || (anim->struct_size & 3u)) return FUIFGPU_E_ARG;
@@ -1039,6 +1357,152 @@ static int read_animation_options(const fuifgpu_animation_options *anim, int w, 
         return fail_with_message(FUIFGPU_E_ARG, "encode_animation: the strip of frames is higher than the format's h holds");
     return FUIFGPU_OK;
 }
+// the option structs of the PNM routes, in the order the entry points have always read them
+int read_picture_options(const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette, const fuifgpu_animation_options *anim_options,
+                         int w, int h, int nch, Lossy &l, PaletteOpts &pal, AnimOpts &anim) {
+    if (!read_lossy_options(lossy, l) || !read_palette_options(palette, nch, pal)) return FUIFGPU_E_ARG;
+    return read_animation_options(anim_options, w, h, anim);
+}
+
+void drop_blobs(uint8_t **blobs_out, size_t *sizes_out, int n) {
+    for (int m = 0; m < n; m++) { free(blobs_out[m]); blobs_out[m] = nullptr; sizes_out[m] = 0; }
+}
+
+// the batch entry points: planes[m] on the host, or (device_input) in device memory
+int encode_images_common(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
+                         const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette, uint8_t **blobs_out, size_t *sizes_out,
+                         bool device_input, const fuifgpu_animation_options *anim_options) {
+    if (!planes || !blobs_out || !sizes_out || n_images < 1 || w < 1 || h < 1 || nch < 1 || nch > 8 || bit_depth < 1 || bit_depth > 14) return FUIFGPU_E_ARG;
+    fuifgpu_encode_options o;
+    Lossy l;
+    PaletteOpts pal;
+    AnimOpts anim;
+    if (const int rc = begin_encode_call(opt, 1, o, [&] { return read_picture_options(lossy, palette, anim_options, w, h, nch, l, pal, anim); })) return rc;
+    for (int m = 0; m < n_images; m++) { blobs_out[m] = nullptr; sizes_out[m] = 0; }
+    for (int m = 0; m < n_images; m++) if (!planes[m]) return FUIFGPU_E_ARG;
+    std::vector<Image> imgs((size_t)n_images);   // (after a failure the pictures before the failed one may hold device-only channels: they go with `imgs`)
+    int rc = FUIFGPU_OK;
+    for (int m = 0; m < n_images && rc == FUIFGPU_OK; m++) rc = build_transformed_image(planes[m], w, h, nch, bit_depth, o, l, pal, anim, imgs[(size_t)m], device_input);
+    if (rc != FUIFGPU_OK) return rc;
+    rc = write_streams_batch(imgs, nch, bit_depth, o, blobs_out, sizes_out);
+    if (rc != FUIFGPU_OK) drop_blobs(blobs_out, sizes_out, n_images);
+    return rc;
+}
+
+// ---- YUV 4:2:0 video frames: what `fuif -y WxH[:b]` writes (import/read_yuv.h:29-63, fuif.cpp:277-283, 309-329, 431-435) ------------------
+// Three channels of unequal geometry from the start -- Y w x h, Cb and Cr (w+1)/2 x (h+1)/2 with hshift = vshift = 1 -- under a transform
+// list that begins [YCbCr, ChromaSubsample{0}] (recorded, not computed); no colour transform, no palettes, no Matching (2dmatch.h:321-322
+// indexes the chroma planes with luma coordinates); from Squeeze on, the end of every input route (squeeze_quantize_and_fetch).
+
+// where plane p (0 Y, 1 Cb, 2 Cr; NV12: 1 = 2 = the plane of pairs) of a frame starts, and the bytes of a clip up to its last sample
+int64_t yuv_plane_at(const YuvGeom &g, int p) { return p == 0 ? 0 : g.pitch_y * g.h + (p == 2 && !g.nv12 ? g.pitch_c * g.ch : 0); }
+int64_t yuv_clip_bytes(const YuvGeom &g) {
+    return (g.nb_frames - 1) * g.frame_bytes + yuv_plane_at(g, 2) + (int64_t)(g.ch - 1) * g.pitch_c + g.row_bytes(true);
+}
+// the three channels as Image(w, h, maxval, 3) + read_YUV_file leave them, frames stacked (fuif.cpp:319-327); no samples yet
+void yuv_image_shell(const YuvGeom &g, int den, Image &img) {
+    img.w = g.w; img.h = g.h * g.nb_frames; img.maxval = g.maxval; img.nb_channels = 3;
+    img.nb_frames = g.nb_frames; img.den = den;
+    img.ch.resize(3);
+    for (int c = 0; c < 3; c++) {
+        Chan &ch = img.ch[c];
+        ch.w = c ? g.cw : g.w; ch.h = (c ? g.ch : g.h) * g.nb_frames;
+        ch.hshift = ch.vshift = c ? 1 : 0;
+        ch.component = c; ch.minval = 0; ch.maxval = g.maxval;
+    }
+    img.transforms.push_back({TR_YCBCR, {}});
+    img.transforms.push_back({TR_SUBSAMPLE, {0}});   // 4:2:0
+    img.stale_tail = true;
+}
+// the host route: read_YUV_file's loops over memory; false: a sample above maxval
+bool unpack_yuv_host(const uint8_t *src, const YuvGeom &g, Image &img) {
+    bool in_range = true;
+    for (int c = 0; c < 3; c++) {
+        Chan &ch = img.ch[c];
+        const int pw = c ? g.cw : g.w, ph = c ? g.ch : g.h;
+        const int64_t pitch = c ? g.pitch_c : g.pitch_y, step = (int64_t)g.bytes * (c && g.nv12 ? 2 : 1), first = c == 2 && g.nv12 ? g.bytes : 0;
+        ch.data.resize((size_t)pw * ph * g.nb_frames);
+        int32_t *dst = ch.data.data();
+        for (int f = 0; f < g.nb_frames; f++)
+            for (int y = 0; y < ph; y++) {
+                const uint8_t *row = src + f * g.frame_bytes + yuv_plane_at(g, c) + y * pitch + first;
+                for (int x = 0; x < pw; x++) {
+                    int32_t v = row[x * step];
+                    if (g.bytes > 1) v += row[x * step + 1] << 8;
+                    in_range &= v <= g.maxval;
+                    *dst++ = v;
+                }
+            }
+    }
+    return in_range;
+}
+// the GPU routes: the raw frames go to the device as they are (or are there already), ONE launch unpacks every plane of every frame of the
+// call into the channels' own buffers, and the staging copies go behind it
+int unpack_yuv_gpu(const void *const *frames, bool on_device, const YuvGeom &g, std::vector<Image> &imgs, bool &in_range) {
+    const int n = (int)imgs.size();
+    std::vector<YuvJob> jobs((size_t)n);
+    std::vector<DevBuf> staged;
+    const size_t clip_bytes = (size_t)yuv_clip_bytes(g);
+    int rc = FUIFGPU_OK;
+    for (int m = 0; m < n && rc == FUIFGPU_OK; m++) {
+        YuvJob &job = jobs[(size_t)m];
+        job.src = static_cast<const uint8_t *>(frames[m]);
+        if (!on_device) {
+            DevBuf dev;
+            if (!dev.alloc(clip_bytes)) { rc = FUIFGPU_E_HIP; break; }
+            g_plane_h2d += clip_bytes;
+            rc = fuifgpu_dev_upload(dev.p, frames[m], clip_bytes);
+            job.src = static_cast<const uint8_t *>(dev.p);
+            staged.push_back(std::move(dev));
+        }
+        for (int c = 0; c < 3 && rc == FUIFGPU_OK; c++) {
+            Chan &ch = imgs[(size_t)m].ch[c];
+            if (!ch.dev.alloc(sizeof(int32_t) * (size_t)ch.w * ch.h)) rc = FUIFGPU_E_HIP;
+            job.out[c] = ch.dev.i32();
+        }
+    }
+    int flag = 0;
+    if (rc == FUIFGPU_OK) rc = unpack_yuv420_gpu(jobs.data(), n, g, &flag);   // (synchronous: the staging copies can go)
+    in_range = flag == 0;
+    return rc;
+}
+
+}  // namespace
+
+int yuv_geometry(const void *yuv_options, int w, int h, int bit_depth, bool one_frame, YuvGeom &g, int *framerate) {
+    fuifgpu_yuv_options y;
+    memset(&y, 0, sizeof(y));
+    if (yuv_options) {
+        const uint32_t sz = static_cast<const fuifgpu_yuv_options *>(yuv_options)->struct_size;
+        if (sz < sizeof(uint32_t) || (sz & 3u)) return fail_with_message(FUIFGPU_E_ARG, "yuv420: struct_size of fuifgpu_yuv_options");
+        memcpy(&y, yuv_options, sz < sizeof(y) ? sz : sizeof(y));
+        if (sz <= offsetof(fuifgpu_yuv_options, nb_frames)) y.nb_frames = 1;   // a struct that ends before the field
+    } else y.nb_frames = 1;
+    if (one_frame) y.nb_frames = 1;
+    if (w < 1 || h < 1 || bit_depth < 8 || bit_depth > 14) return fail_with_message(FUIFGPU_E_ARG, "yuv420: a frame of at least 1 x 1 samples of 8 to 14 bits");
+    if (y.layout != 0 && y.layout != 1) return fail_with_message(FUIFGPU_E_ARG, "yuv420: layout is 0 (I420) or 1 (NV12)");
+    if (y.nb_frames < 1 || y.nb_frames > 65535 || y.framerate < 0) return fail_with_message(FUIFGPU_E_ARG, "yuv420: 1 to 65535 frames, a frame rate of 0 or more");
+    if (y.nb_frames > 1 && (h & 1))
+        return fail_with_message(FUIFGPU_E_ARG, "yuv420: a clip needs an even frame height (the stacked chroma planes would not be (H+1)/2 rows of the strip)");
+    if ((int64_t)w * h * y.nb_frames > INT32_MAX || (int64_t)h * y.nb_frames > INT32_MAX) return fail_with_message(FUIFGPU_E_ARG, "yuv420: more than 2^31-1 samples in a channel");
+    g = YuvGeom{};
+    g.w = w; g.h = h; g.cw = (w + 1) / 2; g.ch = (h + 1) / 2;
+    g.bytes = bit_depth > 8 ? 2 : 1; g.nv12 = y.layout; g.maxval = (1 << bit_depth) - 1; g.nb_frames = y.nb_frames;
+    g.pitch_y = y.pitch_y ? y.pitch_y : g.row_bytes(false);
+    g.pitch_c = y.pitch_c ? y.pitch_c : g.row_bytes(true);
+    if (g.pitch_y < g.row_bytes(false) || g.pitch_c < g.row_bytes(true)) return fail_with_message(FUIFGPU_E_ARG, "yuv420: a row pitch smaller than the row");
+    g.frame_bytes = g.pitch_y * g.h + g.pitch_c * g.ch * (g.nv12 ? 1 : 2);
+    if (framerate) *framerate = y.framerate;
+    return FUIFGPU_OK;
+}
+
+}  // namespace fuifgpu
+
+using namespace fuifgpu;
+
+extern "C" {
+
+void fuifgpu_free_blob(uint8_t *p) { free(p); }
 
 int fuifgpu_encode_plane_traffic(uint64_t *h2d_bytes, uint64_t *d2h_bytes) {
     if (h2d_bytes) *h2d_bytes = g_plane_h2d;
@@ -1085,6 +1549,12 @@ int fuifgpu_quantization_constant(float quality, float chroma_quality, int squee
     if (shift < 0 || !read_qualities(quality, chroma_quality, l)) return -FUIFGPU_E_ARG;
     return l.active ? quantization_constant(l, squeeze_option != 0, chroma_table != 0, shift) : 1;
 }
+int fuifgpu_quantization_constant_yuv(float quality, float chroma_quality, int squeeze_option, int chroma_table, int shift) {
+    Lossy l;
+    if (shift < 0 || !read_qualities(quality, chroma_quality, l)) return -FUIFGPU_E_ARG;
+    l.yuv = true;
+    return l.active ? quantization_constant(l, squeeze_option != 0, chroma_table != 0, shift) : 1;
+}
 
 // planes: nch planes of w*h int32 in [0, 2^bit_depth-1].
 int fuifgpu_encode_animation(const int32_t *planes, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
@@ -1095,21 +1565,13 @@ int fuifgpu_encode_animation(const int32_t *planes, int w, int h, int nch, int b
     Lossy l;
     PaletteOpts pal;
     AnimOpts anim;
-    if (!read_encode_options(opt, o, 0) || !read_lossy_options(lossy, l) || !read_palette_options(palette, nch, pal)) return FUIFGPU_E_ARG;
-    if (const int rc = read_animation_options(anim_options, w, h, anim)) return rc;
-    if (o.max_properties < 0 || o.max_properties > 2 * kMaxRefs) return FUIFGPU_E_ARG;
-    if (o.max_tree_nodes < 1) o.max_tree_nodes = 4095;
-    if (o.max_tree_nodes > kMaxNodes) o.max_tree_nodes = kMaxNodes;
+    if (const int rc = begin_encode_call(opt, 0, o, [&] { return read_picture_options(lossy, palette, anim_options, w, h, nch, l, pal, anim); })) return rc;
     // tree_mode 2 learns with the batch writer's rounds: a batch of one picture, which writes the same bytes (include/fuifgpu.h)
     if (o.tree_mode == 2) return encode_images_common(&planes, 1, w, h, nch, bit_depth, opt, lossy, palette, blob_out, size_out, false, anim_options);
-
-    g_plane_h2d = g_plane_d2h = 0;
-    g_learn_sample_d2h = g_learn_stat_d2h = 0;
     Image img;
-    bool squeezed = false;
-    const int rc = build_transformed_image(planes, w, h, nch, bit_depth, o, l, pal, anim, img, squeezed);
+    const int rc = build_transformed_image(planes, w, h, nch, bit_depth, o, l, pal, anim, img);
     if (rc != FUIFGPU_OK) return rc;
-    return write_stream(img, nch, bit_depth, squeezed, o, blob_out, size_out);
+    return write_stream(std::move(img), nch, bit_depth, o, blob_out, size_out);
 }
 int fuifgpu_encode_image_ex(const int32_t *planes, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
                             const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette, uint8_t **blob_out, size_t *size_out) {
@@ -1136,12 +1598,7 @@ int fuifgpu_encode_channels(const fuifgpu_raw_channel *channels, int n_channels,
         bit_depth < 1 || bit_depth > 14 || (n_transform_words && !transforms))
         return FUIFGPU_E_ARG;
     fuifgpu_encode_options o;
-    if (!read_encode_options(opt, o, 0)) return FUIFGPU_E_ARG;
-    if (o.max_properties < 0 || o.max_properties > 2 * kMaxRefs) return FUIFGPU_E_ARG;
-    if (o.max_tree_nodes < 1) o.max_tree_nodes = 4095;
-    if (o.max_tree_nodes > kMaxNodes) o.max_tree_nodes = kMaxNodes;
-    g_plane_h2d = g_plane_d2h = 0;
-    g_learn_sample_d2h = g_learn_stat_d2h = 0;
+    if (const int rc = begin_encode_call(opt, 0, o, [] { return (int)FUIFGPU_OK; })) return rc;
     Image img;
     img.w = w; img.h = h; img.maxval = (1 << bit_depth) - 1; img.nb_channels = nb_channels;
     img.ch.resize(n_channels);
@@ -1164,526 +1621,67 @@ int fuifgpu_encode_channels(const fuifgpu_raw_channel *channels, int n_channels,
         img.transforms.push_back(t);
         k += 2 + np;
     }
-    bool squeezed = false;
-    if (o.squeeze && (int64_t)img.ch[0].w * img.ch[0].h > 20) {
-        std::vector<int> params = default_squeeze_params(img);
-        fwd_squeeze(img, params);
-        img.transforms.push_back({TR_SQUEEZE, {}});
-        squeezed = true;
-    }
-    return write_stream(img, nb_channels, bit_depth, squeezed, o, blob_out, size_out, /*dct_style=*/true);
+    img.dct_style = true;
+    if (o.squeeze) default_squeeze(img, false);
+    return write_stream(std::move(img), nb_channels, bit_depth, o, blob_out, size_out);
 }
 
-}  // extern "C"
-
-namespace fuifgpu {
-namespace {
-
-// ---- what write_stream and write_streams_batch share --------------------------------------------------------------------------------
-// fuif_prepare_encode (encoding.cpp:737-743): every channel's range from its samples.  Host channels are scanned here; device-only ones
-// (of all pictures) go through ONE k_channel_stats launch, which also counts their zeros for the "predictability" byte
-int channel_ranges(Image *imgs, size_t n_images) {
-    std::vector<StatsRec> recs;
-    std::vector<Chan *> who;
-    for (size_t m = 0; m < n_images; m++)
-        for (Chan &c : imgs[m].ch) {
-            if (!c.resident()) { c.minmax(); continue; }
-            recs.push_back(StatsRec{c.dev, (int64_t)c.w * c.h, 0, 0});
-            who.push_back(&c);
-        }
-    std::vector<int32_t> stats(3 * recs.size());
-    const int rc = channel_stats_gpu(recs.data(), (int)recs.size(), stats.data());
-    for (size_t k = 0; k < who.size() && rc == FUIFGPU_OK; k++) { who[k]->minval = stats[3 * k]; who[k]->maxval = stats[3 * k + 1]; who[k]->zeros = stats[3 * k + 2]; }
-    return rc;
-}
-int group_predictor(const Image &img, int i, bool squeezed, bool dct_style) {  // fuif.cpp:580-588
-    if (i < img.nb_meta) return 3;   // "left" for the palettes
-    if (!squeezed && !dct_style) return 2;
-    return i < img.nb_meta + img.nb_channels ? 2 : 0;
-}
-void responsive_downscales(Image &img, bool squeezed, bool dct_style) {
-    recompute_downscales(img);
-    if (!squeezed && !dct_style) for (int s = 0; s < 6; s++) img.downscales[s] = (int)img.ch.size() - 1;
-}
-// the learner's samples of a picture's device-only groups (what encode_group's sampling loop computes for host channels), in one launch:
-// sample_job[channel] = its job in `out`, -1 for channels that learn nothing or have their samples on the host
-int learn_samples_device(Image &img, bool squeezed, const GroupCoder &gc, LearnSamples &out, std::vector<int> &sample_job) {
-    std::vector<LearnJob> jobs;
-    sample_job.assign(img.ch.size(), -1);
-    for (int i = 0; i < (int)img.ch.size(); i++) {
-        Chan &c = img.ch[i];
-        if (!c.resident() || !c.w || !c.h || c.minval == c.maxval) continue;
-        const LearnPlan lp = plan_learner(c, gc.tree_mode, gc.max_tree_nodes);
-        if (!lp.stride) continue;
-        c.setzero();
-        std::vector<Range> ranges; std::vector<RefInfo> refs;
-        LearnJob job;
-        job.nprops = init_properties(ranges, refs, img, i, i, gc.max_properties);
-        job.n_samples = (int64_t)lp.n_samples; job.stride = (int64_t)lp.stride;
-        const int rc = build_enc_group(c, refs, group_predictor(img, i, squeezed, false), job.g);
-        if (rc != FUIFGPU_OK) return rc;
-        sample_job[(size_t)i] = (int)jobs.size();
-        jobs.push_back(job);
-    }
-    const int rc = learn_samples_jobs_gpu(jobs, out);
-    g_learn_sample_d2h += out.raw.size() * sizeof(int32_t);
-    return rc;
-}
-// tree_mode 2: the trees of every learning group of every picture of the call.  Host-resident channels go to the device here, one phase
-// earlier than for the GPU pixel loop (the same copies); the samples are computed there and stay there.  learned[m][channel]
-int learn_trees_device(std::vector<Image> &imgs, const std::vector<char> &squeezed, const GroupCoder &gc, std::vector<std::vector<std::vector<LearnNode>>> &learned) {
-    std::vector<LearnTreeJob> jobs;
-    std::vector<std::pair<size_t, int>> where;
-    learned.assign(imgs.size(), std::vector<std::vector<LearnNode>>());
-    for (size_t m = 0; m < imgs.size(); m++) {
-        Image &img = imgs[m];
-        learned[m].resize(img.ch.size());
-        for (int i = 0; i < (int)img.ch.size(); i++) {
-            Chan &c = img.ch[i];
-            if (!c.w || !c.h || c.minval == c.maxval) continue;
-            const LearnPlan lp = plan_learner(c, gc.tree_mode, gc.max_tree_nodes);
-            if (!lp.stride) continue;
-            c.setzero();
-            std::vector<Range> ranges; std::vector<RefInfo> refs;
-            LearnTreeJob job;
-            job.sample.nprops = init_properties(ranges, refs, img, i, i, gc.max_properties);
-            job.sample.n_samples = (int64_t)lp.n_samples; job.sample.stride = (int64_t)lp.stride;
-            job.prm.max_nodes = gc.max_tree_nodes; job.prm.max_depth = lp.max_depth; job.prm.min_leaf = lp.min_leaf;
-            job.prm.threshold_bits = (double)gc.split_bits; job.prm.scale = (double)lp.stride;
-            const int rc = build_enc_group(c, refs, group_predictor(img, i, squeezed[m] != 0, false), job.sample.g);
-            if (rc != FUIFGPU_OK) return rc;
-            where.push_back(std::make_pair(m, i));
-            jobs.push_back(std::move(job));
-        }
-    }
-    uint64_t stat_bytes = 0;
-    const int rc = learn_trees_gpu(jobs, &stat_bytes);
-    g_learn_stat_d2h += stat_bytes;
-    for (size_t k = 0; k < jobs.size() && rc == FUIFGPU_OK; k++) learned[where[k].first][(size_t)where[k].second].swap(jobs[k].nodes);
-    return rc;
-}
-// encoding/encoding.cpp:455-470: the fixed header fields into `head`, the transform list into `io`
-void begin_stream(const Image &img, int nch, int bit_depth, const fuifgpu_encode_options &o, Bytes &head, Bytes &io) {
-    for (const char *m = img.nb_frames > 1 ? "FUAF" : "FUIF"; *m; m++) head.put(*m);
-    head.varint((size_t)(nch + '0'));
-    head.varint((size_t)(bit_depth + '&'));
-    head.varint((size_t)(img.w - 1));
-    head.varint((size_t)(img.h - 1));
-    if (img.nb_frames > 1) {   // encoding.cpp:467-473: no per-frame numerators, no loop count
-        head.varint((size_t)(img.nb_frames - 2));
-        head.varint((size_t)(img.den - 1));
-        head.varint(0);
-        head.varint(0);
-    }
-    head.varint(0);  // colormodel
-    head.varint((size_t)o.max_properties);
-    io.varint(img.transforms.size());
-    for (auto &t : img.transforms) {
-        io.varint((size_t)((t.params.size() << 4) + t.id));
-        for (int v : t.params) io.varint((size_t)v);
-    }
-}
-// channel i's group ends at byte `after` of `io`
-void note_responsive(const Image &img, int i, size_t after, int responsive[5]) {
-    for (int s = 0; s < 5; s++) if (img.downscales[s] == i) responsive[s] = (int)after;
-}
-// encoding.cpp:552-573: the responsive offsets behind the header, the groups, the optional index trailer -> one malloc'ed blob
-int finish_stream(Bytes &head, const Bytes &io, int responsive[5], std::vector<GroupEntry> &group_at, bool emit_index, uint8_t **blob_out, size_t *size_out,
-                  const std::vector<uint8_t> &stale = std::vector<uint8_t>()) {
-    int rel = 0;
-    for (int s = 0; s < 5; s++) {
-        if (responsive[s] < 0) responsive[s] = (int)io.b.size();
-        head.varint((size_t)(responsive[s] - rel));
-        rel = responsive[s];
-    }
-    std::vector<uint8_t> trailer;
-    if (emit_index && !group_at.empty()) {
-        // the transform list sits between the header and the first group: offsets become absolute here
-        for (GroupEntry &g : group_at) g.start += (uint32_t)head.b.size();
-        build_index_trailer(group_at, trailer);
-    }
-    const size_t total = head.b.size() + io.b.size() + stale.size() + trailer.size();
-    uint8_t *blob = (uint8_t *)malloc(total ? total : 1);
-    if (!blob) return FUIFGPU_E_NOMEM;
-    memcpy(blob, head.b.data(), head.b.size());
-    memcpy(blob + head.b.size(), io.b.data(), io.b.size());
-    if (!stale.empty()) memcpy(blob + head.b.size() + io.b.size(), stale.data(), stale.size());   // (Image::stale_tail)
-    if (!trailer.empty()) memcpy(blob + head.b.size() + io.b.size() + stale.size(), trailer.data(), trailer.size());
-    *blob_out = blob;
-    *size_out = total;
-    return FUIFGPU_OK;
-}
-
-int write_stream(Image &img, int nch, int bit_depth, bool squeezed, const fuifgpu_encode_options &o, uint8_t **blob_out, size_t *size_out,
-                 bool dct_style) {
-    if (o.tree_mode == 2)   // (fuifgpu_encode_channels; every other entry point takes tree_mode 2 to the batch writer)
-        return fail_with_message(FUIFGPU_E_UNSUPPORTED, "tree_mode 2 (trees learned with GPU statistics) is not offered for channels in a transform domain: use tree_mode 1");
-    EncScratch enc_scratch;
-    struct DevCleanup {   // device copies of the channels and the coder's buffers live as long as this call
-        Image &img; EncScratch &s;
-        ~DevCleanup() { for (Chan &c : img.ch) { if (c.dev) fuifgpu_dev_free(c.dev); c.dev = nullptr; } s.release(); }
-    } dev_cleanup{img, enc_scratch};
-    int gpu_rc = channel_ranges(&img, 1);
-    if (gpu_rc != FUIFGPU_OK) return gpu_rc;
-    responsive_downscales(img, squeezed, dct_style);
-
-    std::vector<uint16_t> tables(16384);
-    build_chance_table(tables.data(), 0xFFFFFFFFu / 19, 2);
-    build_chance_table(tables.data() + 8192, 0x0d000000u, 6);
-    GroupCoder gc{tables.data(), tables.data() + 8192, o.max_properties, o.tree_mode, o.max_tree_nodes, o.split_bits > 0 ? o.split_bits : 0};
-    gc.gpu_entropy = o.gpu_entropy != 0; gc.scratch = &enc_scratch; gc.gpu_rc = &gpu_rc;
-
-    // encoding/encoding.cpp:455-573
-    Bytes head, io;
-    begin_stream(img, nch, bit_depth, o, head, io);
-    int responsive[5] = {-1, -1, -1, -1, -1};
-    std::vector<GroupEntry> group_at;  // group starts relative to `io` (made absolute below)
-    StaleTail stale;
-    const int n = (int)img.ch.size();
-    for (int i = 0; i < n; i++) {
-        Chan &c = img.ch[i];
-        if (!c.w || !c.h) continue;
-        const int predictor = group_predictor(img, i, squeezed, dct_style);
-        size_t header_pos = 0;
-        size_t before = io.b.size();
-        group_at.push_back(GroupEntry{(uint32_t)before, i});
-        size_t body = encode_group(io, img, i, predictor, true, gc, header_pos);
-        float bits = body * 8.0f, pixels = (float)c.w * c.h, ubits = 0.0f;
-        if (c.maxval > c.minval) ubits = pixels * (ilog2u((uint32_t)(c.maxval - c.minval)) + 1) + 16;
-        if (bits >= ubits) {
-            // encoding.cpp:545-551: roll back, store uncompressed; a trivial channel: the reference re-encodes it "uncompressed" too (compress bit = 0)
-            if (img.stale_tail) stale.abandoned(before, io.b.data() + before, io.b.size() - before);
-            io.b.resize(before);
-            encode_group(io, img, i, predictor, false, gc, header_pos);
-        }
-        note_responsive(img, i, io.b.size(), responsive);
-    }
-    if (gpu_rc != FUIFGPU_OK) return gpu_rc;   // no host route behind the GPU pixel loop: the caller asked for it
-    return finish_stream(head, io, responsive, group_at, o.emit_index != 0, blob_out, size_out, stale.behind(io.b.size()));
-}
-
-
-// ---- a batch of pictures: every compressed group's pixel loop in ONE launch pair ------------------------------------------------
-// Phase 1 (host, per picture): header fields, per group the header + zero chance + learned tree into its own byte buffer, the
-// coder's state behind the tree.  Phase 2 (GPU): maniac_encode_jobs_gpu -- the context model of every pixel of every group in
-// one launch, then one wavefront per group.  Phase 3 (host, per picture): flush, the roll-back to "uncompressed" of
-// encoding.cpp:545-551, responsive offsets, group index.  Same bytes as write_stream picture by picture.
-// Device-only channels (fuifgpu_encode_images_device) take the same three phases: their ranges and zero counts come from one
-// statistics launch, the learner's samples of a picture from one k_learn_samples_jobs launch, and build_enc_group hands their
-// buffers to the coder as they are; only a group that is rolled back comes to the host.
-struct PendingGroup {
-    int channel = 0, predictor = 0, job = -1;   // job -1: a trivial channel (no coder)
-    Bytes prefix;
-    size_t header_len = 0;
-};
-int write_streams_batch(std::vector<Image> &imgs, int nch, int bit_depth, const std::vector<char> &squeezed, const fuifgpu_encode_options &o,
-                        uint8_t **blobs_out, size_t *sizes_out) {
-    struct DevCleanup {
-        std::vector<Image> &imgs;
-        ~DevCleanup() { for (Image &im : imgs) for (Chan &c : im.ch) { if (c.dev) fuifgpu_dev_free(c.dev); c.dev = nullptr; } }
-    } dev_cleanup{imgs};
-    std::vector<uint16_t> tables(16384);
-    build_chance_table(tables.data(), 0xFFFFFFFFu / 19, 2);
-    build_chance_table(tables.data() + 8192, 0x0d000000u, 6);
-    GroupCoder gc{tables.data(), tables.data() + 8192, o.max_properties, o.tree_mode, o.max_tree_nodes, o.split_bits > 0 ? o.split_bits : 0};
-    if (o.tree_mode == 2) {   // no silent host route: without a device the call fails whatever the pictures hold
-        int n_devices = 0;
-        const int rc = fuifgpu_device_count(&n_devices);
-        if (rc != FUIFGPU_OK) return rc;
-    }
-    int gpu_rc = channel_ranges(imgs.data(), imgs.size());
-    if (gpu_rc != FUIFGPU_OK) return gpu_rc;
-    gc.gpu_rc = &gpu_rc;
-    std::vector<std::vector<std::vector<LearnNode>>> learned;
-    if (gc.tree_mode == 2) {
-        const int rc = learn_trees_device(imgs, squeezed, gc, learned);
-        if (rc != FUIFGPU_OK) return rc;
-    }
-    std::vector<EncJob> jobs;
-    std::vector<std::vector<PendingGroup>> pending(imgs.size());
-    for (size_t m = 0; m < imgs.size(); m++) {
-        Image &img = imgs[m];
-        responsive_downscales(img, squeezed[m] != 0, false);
-        LearnSamples samples;
-        std::vector<int> sample_job;
-        const int rc = gc.tree_mode == 2 ? FUIFGPU_OK : learn_samples_device(img, squeezed[m] != 0, gc, samples, sample_job);
-        if (rc != FUIFGPU_OK) return rc;
-        gc.samples = &samples; gc.sample_job = &sample_job;
-        gc.learned = gc.tree_mode == 2 ? &learned[m] : nullptr;
-        for (int i = 0; i < (int)img.ch.size(); i++) {
-            Chan &c = img.ch[i];
-            if (!c.w || !c.h) continue;
-            PendingGroup pg;
-            pg.channel = i;
-            pg.predictor = group_predictor(img, i, squeezed[m] != 0, false);
-            if (c.minval != c.maxval) {
-                EncJob job;
-                encode_group(pg.prefix, img, i, pg.predictor, true, gc, pg.header_len, &job);
-                pg.job = (int)jobs.size();
-                jobs.push_back(std::move(job));
-            }
-            pending[m].push_back(std::move(pg));
-        }
-        gc.samples = nullptr; gc.sample_job = nullptr; gc.learned = nullptr;
-    }
-    if (gpu_rc != FUIFGPU_OK) return gpu_rc;
-    int rc = maniac_encode_jobs_gpu(jobs, gc.pixel_table);
-    if (rc != FUIFGPU_OK) return rc;
-    for (size_t m = 0; m < imgs.size(); m++) {
-        Image &img = imgs[m];
-        Bytes head, io;
-        begin_stream(img, nch, bit_depth, o, head, io);
-        int responsive[5] = {-1, -1, -1, -1, -1};
-        std::vector<GroupEntry> group_at;
-        StaleTail stale;
-        for (PendingGroup &pg : pending[m]) {
-            const int i = pg.channel;
-            Chan &c = img.ch[i];
-            const size_t before = io.b.size();
-            group_at.push_back(GroupEntry{(uint32_t)before, i});
-            bool uncompressed = pg.job < 0;   // a trivial channel: the reference re-encodes it with the compress bit off
-            if (!uncompressed) {
-                EncJob &job = jobs[(size_t)pg.job];
-                Bytes g = pg.prefix;
-                g.b.insert(g.b.end(), job.body.begin(), job.body.end());
-                RacEnc rac(g);
-                rac.range = job.state.range; rac.low = job.state.low; rac.delayed = job.state.delayed; rac.pending = job.state.pending;
-                rac.flush();
-                const float bits = (g.b.size() - pg.header_len) * 8.0f, pixels = (float)c.w * c.h;
-                const float ubits = pixels * (ilog2u((uint32_t)(c.maxval - c.minval)) + 1) + 16;
-                if (bits >= ubits) {   // encoding.cpp:545-551: roll back, store uncompressed
-                    uncompressed = true;
-                    if (img.stale_tail) stale.abandoned(before, g.b.data(), g.b.size());
-                } else io.b.insert(io.b.end(), g.b.begin(), g.b.end());
-            }
-            if (uncompressed) {
-                size_t header_pos = 0;
-                encode_group(io, img, i, pg.predictor, false, gc, header_pos);   // (a device-only channel comes to the host here)
-            }
-            note_responsive(img, i, io.b.size(), responsive);
-        }
-        if (gpu_rc != FUIFGPU_OK) return gpu_rc;
-        rc = finish_stream(head, io, responsive, group_at, o.emit_index != 0, &blobs_out[m], &sizes_out[m], stale.behind(io.b.size()));
-        if (rc != FUIFGPU_OK) return rc;
-    }
-    return FUIFGPU_OK;
-}
-
-}  // namespace
-}  // namespace fuifgpu
-
-// the batch entry points: planes[m] on the host, or (device_input) in device memory
-static int encode_images_common(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
-                                const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette, uint8_t **blobs_out, size_t *sizes_out,
-                                bool device_input, const fuifgpu_animation_options *anim_options) {
-    if (!planes || !blobs_out || !sizes_out || n_images < 1 || w < 1 || h < 1 || nch < 1 || nch > 8 || bit_depth < 1 || bit_depth > 14) return FUIFGPU_E_ARG;
-    fuifgpu_encode_options o;
-    Lossy l;
-    PaletteOpts pal;
-    if (!read_encode_options(opt, o, 1) || !read_lossy_options(lossy, l) || !read_palette_options(palette, nch, pal)) return FUIFGPU_E_ARG;
-    AnimOpts anim;
-    if (const int arc = read_animation_options(anim_options, w, h, anim)) return arc;
-    if (o.max_properties < 0 || o.max_properties > 2 * kMaxRefs) return FUIFGPU_E_ARG;
-    if (o.max_tree_nodes < 1) o.max_tree_nodes = 4095;
-    if (o.max_tree_nodes > kMaxNodes) o.max_tree_nodes = kMaxNodes;
-    for (int m = 0; m < n_images; m++) { blobs_out[m] = nullptr; sizes_out[m] = 0; }
-    for (int m = 0; m < n_images; m++) if (!planes[m]) return FUIFGPU_E_ARG;
-    g_plane_h2d = g_plane_d2h = 0;
-    g_learn_sample_d2h = g_learn_stat_d2h = 0;
-    std::vector<Image> imgs((size_t)n_images);
-    std::vector<char> squeezed((size_t)n_images, 0);
-    int rc = FUIFGPU_OK;
-    for (int m = 0; m < n_images && rc == FUIFGPU_OK; m++) {
-        bool sq = false;
-        rc = build_transformed_image(planes[m], w, h, nch, bit_depth, o, l, pal, anim, imgs[(size_t)m], sq, device_input);
-        squeezed[(size_t)m] = sq ? 1 : 0;
-    }
-    if (rc != FUIFGPU_OK) {   // (the pictures before the failed one may hold device-only channels)
-        for (Image &im : imgs) for (Chan &c : im.ch) { if (c.dev) fuifgpu_dev_free(c.dev); c.dev = nullptr; }
-        return rc;
-    }
-    rc = write_streams_batch(imgs, nch, bit_depth, squeezed, o, blobs_out, sizes_out);
-    if (rc != FUIFGPU_OK) for (int m = 0; m < n_images; m++) { free(blobs_out[m]); blobs_out[m] = nullptr; sizes_out[m] = 0; }
-    return rc;
-}
-extern "C" int fuifgpu_encode_images_lossy(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth,
-                                           const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out) {
+int fuifgpu_encode_images_lossy(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
+                                const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out) {
     return encode_images_common(planes, n_images, w, h, nch, bit_depth, opt, lossy, nullptr, blobs_out, sizes_out, false, nullptr);
 }
-extern "C" int fuifgpu_encode_images_ex(const int32_t *const *planes, int planes_on_device, int n_images, int w, int h, int nch, int bit_depth,
-                                        const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette,
-                                        uint8_t **blobs_out, size_t *sizes_out) {
+int fuifgpu_encode_images_ex(const int32_t *const *planes, int planes_on_device, int n_images, int w, int h, int nch, int bit_depth,
+                             const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette,
+                             uint8_t **blobs_out, size_t *sizes_out) {
     return encode_images_common(planes, n_images, w, h, nch, bit_depth, opt, lossy, palette, blobs_out, sizes_out, planes_on_device != 0, nullptr);
 }
-extern "C" int fuifgpu_encode_animations(const int32_t *const *frames, int on_device, int n_clips, int w, int frame_h, int nch, int bit_depth,
-                                         const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette,
-                                         const fuifgpu_animation_options *anim, uint8_t **blobs_out, size_t *sizes_out) {
+int fuifgpu_encode_animations(const int32_t *const *frames, int on_device, int n_clips, int w, int frame_h, int nch, int bit_depth,
+                              const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, const fuifgpu_palette_options *palette,
+                              const fuifgpu_animation_options *anim, uint8_t **blobs_out, size_t *sizes_out) {
     return encode_images_common(frames, n_clips, w, frame_h, nch, bit_depth, opt, lossy, palette, blobs_out, sizes_out, on_device != 0, anim);
 }
-extern "C" int fuifgpu_encode_images(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
-                                     uint8_t **blobs_out, size_t *sizes_out) {
+int fuifgpu_encode_images(const int32_t *const *planes, int n_images, int w, int h, int nch, int bit_depth, const fuifgpu_encode_options *opt,
+                          uint8_t **blobs_out, size_t *sizes_out) {
     return fuifgpu_encode_images_lossy(planes, n_images, w, h, nch, bit_depth, opt, nullptr, blobs_out, sizes_out);
 }
-extern "C" int fuifgpu_encode_images_device(const int32_t *const *planes_device, int n_images, int w, int h, int nch, int bit_depth,
-                                            const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out) {
+int fuifgpu_encode_images_device(const int32_t *const *planes_device, int n_images, int w, int h, int nch, int bit_depth,
+                                 const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out) {
     return encode_images_common(planes_device, n_images, w, h, nch, bit_depth, opt, lossy, nullptr, blobs_out, sizes_out, true, nullptr);
 }
 
-// ---- YUV 4:2:0 video frames: what `fuif -y WxH[:b]` writes (import/read_yuv.h:29-63, fuif.cpp:277-283, 309-329, 431-435) ------------------
-// Three channels of unequal geometry from the start -- Y w x h, Cb and Cr (w+1)/2 x (h+1)/2 with hshift = vshift = 1 -- under a transform
-// list that begins [YCbCr, ChromaSubsample{0}] (recorded, not computed); no colour transform, no palettes, no Matching (2dmatch.h:321-322
-// indexes the chroma planes with luma coordinates); from Squeeze on, the end of every input route (squeeze_quantize_and_fetch).
-namespace fuifgpu {
-int yuv_geometry(const void *yuv_options, int w, int h, int bit_depth, bool one_frame, YuvGeom &g, int *framerate) {
-    fuifgpu_yuv_options y;
-    memset(&y, 0, sizeof(y));
-    if (yuv_options) {
-        const uint32_t sz = static_cast<const fuifgpu_yuv_options *>(yuv_options)->struct_size;
-        if (sz < sizeof(uint32_t) || (sz & 3u)) return fail_with_message(FUIFGPU_E_ARG, "yuv420: struct_size of fuifgpu_yuv_options");
-        memcpy(&y, yuv_options, sz < sizeof(y) ? sz : sizeof(y));
-        if (sz <= offsetof(fuifgpu_yuv_options, nb_frames)) y.nb_frames = 1;   // a struct that ends before the field
-    } else y.nb_frames = 1;
-    if (one_frame) y.nb_frames = 1;
-    if (w < 1 || h < 1 || bit_depth < 8 || bit_depth > 14) return fail_with_message(FUIFGPU_E_ARG, "yuv420: a frame of at least 1 x 1 samples of 8 to 14 bits");
-    if (y.layout != 0 && y.layout != 1) return fail_with_message(FUIFGPU_E_ARG, "yuv420: layout is 0 (I420) or 1 (NV12)");
-    if (y.nb_frames < 1 || y.nb_frames > 65535 || y.framerate < 0) return fail_with_message(FUIFGPU_E_ARG, "yuv420: 1 to 65535 frames, a frame rate of 0 or more");
-    if (y.nb_frames > 1 && (h & 1))
-        return fail_with_message(FUIFGPU_E_ARG, "yuv420: a clip needs an even frame height (the stacked chroma planes would not be (H+1)/2 rows of the strip)");
-    if ((int64_t)w * h * y.nb_frames > INT32_MAX || (int64_t)h * y.nb_frames > INT32_MAX) return fail_with_message(FUIFGPU_E_ARG, "yuv420: more than 2^31-1 samples in a channel");
-    g = YuvGeom{};
-    g.w = w; g.h = h; g.cw = (w + 1) / 2; g.ch = (h + 1) / 2;
-    g.bytes = bit_depth > 8 ? 2 : 1; g.nv12 = y.layout; g.maxval = (1 << bit_depth) - 1; g.nb_frames = y.nb_frames;
-    g.pitch_y = y.pitch_y ? y.pitch_y : g.row_bytes(false);
-    g.pitch_c = y.pitch_c ? y.pitch_c : g.row_bytes(true);
-    if (g.pitch_y < g.row_bytes(false) || g.pitch_c < g.row_bytes(true)) return fail_with_message(FUIFGPU_E_ARG, "yuv420: a row pitch smaller than the row");
-    g.frame_bytes = g.pitch_y * g.h + g.pitch_c * g.ch * (g.nv12 ? 1 : 2);
-    if (framerate) *framerate = y.framerate;
-    return FUIFGPU_OK;
-}
-}  // namespace fuifgpu
-
-// where plane p (0 Y, 1 Cb, 2 Cr; NV12: 1 = 2 = the plane of pairs) of a frame starts, and the bytes of a clip up to its last sample
-static int64_t yuv_plane_at(const fuifgpu::YuvGeom &g, int p) { return p == 0 ? 0 : g.pitch_y * g.h + (p == 2 && !g.nv12 ? g.pitch_c * g.ch : 0); }
-static int64_t yuv_clip_bytes(const fuifgpu::YuvGeom &g) {
-    return (g.nb_frames - 1) * g.frame_bytes + yuv_plane_at(g, 2) + (int64_t)(g.ch - 1) * g.pitch_c + g.row_bytes(true);
-}
-// the three channels as Image(w, h, maxval, 3) + read_YUV_file leave them, frames stacked (fuif.cpp:319-327); no samples yet
-static void yuv_image_shell(const fuifgpu::YuvGeom &g, int den, fuifgpu::Image &img) {
-    using namespace fuifgpu;
-    img.w = g.w; img.h = g.h * g.nb_frames; img.maxval = g.maxval; img.nb_channels = 3;
-    img.nb_frames = g.nb_frames; img.den = den;
-    img.ch.resize(3);
-    for (int c = 0; c < 3; c++) {
-        Chan &ch = img.ch[c];
-        ch.w = c ? g.cw : g.w; ch.h = (c ? g.ch : g.h) * g.nb_frames;
-        ch.hshift = ch.vshift = c ? 1 : 0;
-        ch.component = c; ch.minval = 0; ch.maxval = g.maxval;
-    }
-    img.transforms.push_back({TR_YCBCR, {}});
-    img.transforms.push_back({TR_SUBSAMPLE, {0}});   // 4:2:0
-    img.stale_tail = true;
-}
-// the host route: read_YUV_file's loops over memory; false: a sample above maxval
-static bool unpack_yuv_host(const uint8_t *src, const fuifgpu::YuvGeom &g, fuifgpu::Image &img) {
-    bool in_range = true;
-    for (int c = 0; c < 3; c++) {
-        fuifgpu::Chan &ch = img.ch[c];
-        const int pw = c ? g.cw : g.w, ph = c ? g.ch : g.h;
-        const int64_t pitch = c ? g.pitch_c : g.pitch_y, step = (int64_t)g.bytes * (c && g.nv12 ? 2 : 1), first = c == 2 && g.nv12 ? g.bytes : 0;
-        ch.data.resize((size_t)pw * ph * g.nb_frames);
-        int32_t *dst = ch.data.data();
-        for (int f = 0; f < g.nb_frames; f++)
-            for (int y = 0; y < ph; y++) {
-                const uint8_t *row = src + f * g.frame_bytes + yuv_plane_at(g, c) + y * pitch + first;
-                for (int x = 0; x < pw; x++) {
-                    int32_t v = row[x * step];
-                    if (g.bytes > 1) v += row[x * step + 1] << 8;
-                    in_range &= v <= g.maxval;
-                    *dst++ = v;
-                }
-            }
-    }
-    return in_range;
-}
-
-extern "C" int fuifgpu_quantization_constant_yuv(float quality, float chroma_quality, int squeeze_option, int chroma_table, int shift) {
-    Lossy l;
-    if (shift < 0 || !read_qualities(quality, chroma_quality, l)) return -FUIFGPU_E_ARG;
-    l.yuv = true;
-    return l.active ? quantization_constant(l, squeeze_option != 0, chroma_table != 0, shift) : 1;
-}
-
-extern "C" int fuifgpu_encode_yuv420(const void *const *frames, int on_device, int n, int w, int h, int bit_depth, const fuifgpu_yuv_options *yuv,
-                                     const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out) {
+int fuifgpu_encode_yuv420(const void *const *frames, int on_device, int n, int w, int h, int bit_depth, const fuifgpu_yuv_options *yuv,
+                          const fuifgpu_encode_options *opt, const fuifgpu_lossy_options *lossy, uint8_t **blobs_out, size_t *sizes_out) {
     if (!frames || !blobs_out || !sizes_out || n < 1) return FUIFGPU_E_ARG;
     for (int m = 0; m < n; m++) { blobs_out[m] = nullptr; sizes_out[m] = 0; }
     fuifgpu_encode_options o;
     Lossy l;
-    if (!read_encode_options(opt, o, on_device ? 1 : 0) || !read_lossy_options(lossy, l)) return FUIFGPU_E_ARG;
-    l.yuv = true;
     YuvGeom g;
     int framerate = 0;
-    if (const int rc = yuv_geometry(yuv, w, h, bit_depth, false, g, &framerate)) return rc;
-    if (o.max_properties < 0 || o.max_properties > 2 * kMaxRefs) return FUIFGPU_E_ARG;
-    if (o.max_tree_nodes < 1) o.max_tree_nodes = 4095;
-    if (o.max_tree_nodes > kMaxNodes) o.max_tree_nodes = kMaxNodes;
+    if (const int rc = begin_encode_call(opt, on_device ? 1 : 0, o, [&] {
+            if (!read_lossy_options(lossy, l)) return (int)FUIFGPU_E_ARG;
+            return yuv_geometry(yuv, w, h, bit_depth, false, g, &framerate);
+        }))
+        return rc;
+    l.yuv = true;
     for (int m = 0; m < n; m++)
         if (!frames[m]) return fail_with_message(FUIFGPU_E_ARG, "yuv420: a NULL frame");
     const bool on_gpu = on_device != 0 || o.gpu_forward != 0;
     const int den = framerate > 0 ? framerate : 10;   // fuif.cpp:335; image.h: den = 10
-    g_plane_h2d = g_plane_d2h = 0;
-    g_learn_sample_d2h = g_learn_stat_d2h = 0;
     std::vector<Image> imgs((size_t)n);
-    std::vector<char> squeezed((size_t)n, 0);
-    auto release = [&]() { for (Image &im : imgs) for (Chan &c : im.ch) { if (c.dev) fuifgpu_dev_free(c.dev); c.dev = nullptr; } };
     int rc = FUIFGPU_OK;
     bool in_range = true;
     for (Image &im : imgs) yuv_image_shell(g, den, im);
-    if (!on_gpu) {
-        for (int m = 0; m < n; m++) in_range &= unpack_yuv_host(static_cast<const uint8_t *>(frames[m]), g, imgs[(size_t)m]);
-    } else {
-        // the raw frames go to the device as they are (or are there already), ONE launch unpacks every plane of every frame of the call
-        // into the channels' own buffers, and the staging copies go
-        std::vector<YuvJob> jobs((size_t)n);
-        std::vector<void *> staged;
-        const size_t clip_bytes = (size_t)yuv_clip_bytes(g);
-        for (int m = 0; m < n && rc == FUIFGPU_OK; m++) {
-            YuvJob &job = jobs[(size_t)m];
-            job.src = static_cast<const uint8_t *>(frames[m]);
-            if (!on_device) {
-                void *dev = fuifgpu_dev_alloc(clip_bytes);
-                if (!dev) { rc = FUIFGPU_E_HIP; break; }
-                staged.push_back(dev);
-                g_plane_h2d += clip_bytes;
-                rc = fuifgpu_dev_upload(dev, frames[m], clip_bytes);
-                job.src = static_cast<const uint8_t *>(dev);
-            }
-            for (int c = 0; c < 3 && rc == FUIFGPU_OK; c++) {
-                Chan &ch = imgs[(size_t)m].ch[c];
-                ch.dev = (int32_t *)fuifgpu_dev_alloc(sizeof(int32_t) * (size_t)ch.w * ch.h);
-                if (!ch.dev) rc = FUIFGPU_E_HIP;
-                job.out[c] = ch.dev;
-            }
-        }
-        int flag = 0;
-        if (rc == FUIFGPU_OK) rc = unpack_yuv420_gpu(jobs.data(), n, g, &flag);   // (synchronous: the staging copies can go)
-        for (void *p : staged) fuifgpu_dev_free(p);
-        in_range = flag == 0;
-    }
+    if (on_gpu) rc = unpack_yuv_gpu(frames, on_device != 0, g, imgs, in_range);
+    else for (int m = 0; m < n; m++) in_range &= unpack_yuv_host(static_cast<const uint8_t *>(frames[m]), g, imgs[(size_t)m]);
     if (rc == FUIFGPU_OK && !in_range) rc = fail_with_message(FUIFGPU_E_ARG, "yuv420: a sample above 2^bit_depth - 1");
-    for (int m = 0; m < n && rc == FUIFGPU_OK; m++) {
-        bool sq = false;
-        rc = squeeze_quantize_and_fetch(imgs[(size_t)m], o, l, true, on_gpu, on_device != 0, sq, rc);
-        squeezed[(size_t)m] = sq ? 1 : 0;
-    }
-    if (rc != FUIFGPU_OK) { release(); return rc; }
+    for (int m = 0; m < n && rc == FUIFGPU_OK; m++) rc = squeeze_quantize_and_fetch(imgs[(size_t)m], o, l, true, on_gpu, on_device != 0, rc);
+    if (rc != FUIFGPU_OK) return rc;
     // pictures in device memory stay there until their last coded byte: the batch writer; so does a batch whose pixel loops run on the
     // GPU (one launch pair for all of them); else picture by picture through the stream writer of fuifgpu_encode_image
-    if (on_device || (o.gpu_entropy && n > 1) || o.tree_mode == 2) rc = write_streams_batch(imgs, 3, bit_depth, squeezed, o, blobs_out, sizes_out);
-    else for (int m = 0; m < n && rc == FUIFGPU_OK; m++) rc = write_stream(imgs[(size_t)m], 3, bit_depth, squeezed[(size_t)m] != 0, o, &blobs_out[m], &sizes_out[m]);
-    if (rc != FUIFGPU_OK) {
-        release();
-        for (int m = 0; m < n; m++) { free(blobs_out[m]); blobs_out[m] = nullptr; sizes_out[m] = 0; }
-    }
+    if (on_device || (o.gpu_entropy && n > 1) || o.tree_mode == 2) rc = write_streams_batch(imgs, 3, bit_depth, o, blobs_out, sizes_out);
+    else for (int m = 0; m < n && rc == FUIFGPU_OK; m++) rc = write_stream(std::move(imgs[(size_t)m]), 3, bit_depth, o, &blobs_out[m], &sizes_out[m]);
+    if (rc != FUIFGPU_OK) drop_blobs(blobs_out, sizes_out, n);
     return rc;
 }
+
+}  // extern "C"
